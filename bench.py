@@ -61,7 +61,17 @@ def parse():
     ap.add_argument("--dry_run", action="store_true",
                     help="rank plumbing only (spawn, rendezvous, barrier, max-over-ranks timing, the JSON line) with no "
                          "GPU work: what the CPU/gloo test of --gpus N exercises")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy (float32, at most "
+                         "64 MB in all; rank 0's shard): ppo = the network after the update, the action variance and the "
+                         "rollout the update trained on (wide arrays as a fixed, seeded sample of rows); dqn = both networks, "
+                         "the TD loss and the recorded step.  Inputs are seeded: two builds compare output for output")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.dry_run:
+        ap.error("--dump-outputs: a dry run computes nothing")
+    return a
 
 
 def spawn_ranks(a):
@@ -155,6 +165,66 @@ def make_args(n, **kw):
 
 def quiet():
     return contextlib.redirect_stdout(io.StringIO())
+
+
+DUMP_LIMIT_BYTES = 64 << 20        # --dump-outputs: all files together
+DUMP_SAMPLE_ROWS = 65536           # rows kept of a wide rollout array [T, N, width] (T * N <= 655 360 at any num_envs)
+
+
+def sample_rows(t, k=DUMP_SAMPLE_ROWS, seed=0):
+    """A fixed, seeded choice of `k` rows of `t` viewed as [rows, last dim], in row order: the same rows for the same
+    shape, so arrays sampled with the same `seed` stay aligned row for row."""
+    import numpy as np
+    rows = t.reshape(-1, t.shape[-1])
+    if rows.shape[0] <= k:
+        return rows
+    idx = np.sort(np.random.default_rng(seed).choice(rows.shape[0], k, replace=False))
+    return rows.index_select(0, torch.from_numpy(idx).to(rows.device))
+
+
+def dump_outputs(out_dir, arrays):
+    """Write every array of `arrays` as out_dir/<name>.npy: float64 stays float64, everything else becomes float32.
+    Refuses (before writing anything) a set larger than DUMP_LIMIT_BYTES.  Returns what was written."""
+    import numpy as np
+    host = {}
+    for name, v in arrays.items():
+        a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        host[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError("--dump-outputs: %d bytes over the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "arrays": len(host), "bytes": total}
+
+
+def ppo_outputs(agent):
+    """What one PPO iteration leaves its caller: the network after the update (state_dict names), the decayed action
+    variance, and the rollout the update trained on -- rewards, log-probs, TD targets, advantages and the last step's
+    done mask in full, next observations and actions as the same sample of rollout rows."""
+    T, n = agent.rollout_size, int(agent.args.num_envs)
+    out = {"param." + k: v for k, v in agent.net.state_dict().items()}
+    out["action_var"] = agent.action_var
+    out["reward"] = agent.all_reward.view(T, n)
+    out["log_prob"] = agent.all_log_prob
+    out["target"] = agent._target.view(T, n)
+    out["advantage"] = agent.all_advantage.view(T, n)
+    out["done"] = agent.all_done.reshape(n)
+    out["next_obs"] = sample_rows(agent.all_next_obs)
+    out["action"] = sample_rows(agent.all_acts)
+    return out
+
+
+def dqn_outputs(agent):
+    """What the last DQN.run() leaves its caller: both networks after its update, its TD loss, and the step it recorded."""
+    out = {"q." + k: v for k, v in agent.q.state_dict().items()}
+    out.update({"q_target." + k: v for k, v in agent.q_target.state_dict().items()})
+    rp = agent.replay
+    h = (rp.head - 1) % rp.capacity
+    out.update(loss=agent.last_loss.reshape(1), action=rp.action[h], reward=rp.reward[h], done=rp.done[h],
+               next_obs=rp.next_obs[h])
+    return out
 
 
 def _time_launches(fn, reps):
@@ -703,7 +773,7 @@ DQN_FWD_FLOP = 2 * (73 * 256 + 256 * 256 + 256 * 18)            # 177 664 per sa
 DQN_BWD_DX_FLOP = 2 * (18 * 256 + 256 * 256)                     # 140 288
 
 
-def dqn_measure(n, mb, warmup, steps, kernel_reps, gemm=None):
+def dqn_measure(n, mb, warmup, steps, kernel_reps, gemm=None, dump_dir=None):
     """BASELINE configs[4]: DQN, 32768 envs, HBM-resident replay ring (stated capacity), per-env eps-greedy and
     Huber-TD on the HIP kernels.  A "step" = one DQN.run(): act (one launch), env step, record into the ring,
     one update on `dqn_mini_batch` sampled steps x num_envs rows (dqn.py:102-126).  One rank (the reference DQN
@@ -726,6 +796,7 @@ def dqn_measure(n, mb, warmup, steps, kernel_reps, gemm=None):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     assert int(agent.packed.step.item()) == warmup + steps, "an update was skipped"
+    dumped = dump_outputs(dump_dir, dqn_outputs(agent)) if dump_dir else None
     h2_refused = int(agent.h2_overflows)
     recon_form = bool(getattr(agent, "dw2_recon", False))
     finite = all(torch.isfinite(p).all().item() for p in agent.q.parameters())
@@ -811,7 +882,7 @@ def dqn_measure(n, mb, warmup, steps, kernel_reps, gemm=None):
     agent.exit()
     del agent
     torch.cuda.empty_cache()
-    return {
+    line = {
         "metric": "env-steps/sec (DQN act + env step + update), %d envs" % n, "value": round(n * steps / elapsed, 1),
         "unit": "env-steps/s", "n_gpus": 1, "steps": steps, "warmup": warmup, "ms_per_step": round(elapsed / steps * 1e3, 3),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype, "data": "synthetic",
@@ -823,12 +894,16 @@ def dqn_measure(n, mb, warmup, steps, kernel_reps, gemm=None):
                    "rows_per_update": n * mb, "replay_capacity_steps": capacity, "replay_bytes": rbytes,
                    "updates_per_env_step": 1, "parallelism": "dp1"},
         "params_finite": finite, "roofline": ks[0], "kernels": ks[1:]}
+    if dumped:
+        line["dumped_outputs"] = dumped
+    return line
 
 
 def dqn_bench(a):
     if a.gpus != 1:
         sys.exit("bench.py --workload dqn runs on one GPU")
-    print(json.dumps(dqn_measure(a.dqn_envs, a.dqn_mini_batch, a.warmup, a.steps, a.kernel_reps, a.dqn_gemm)), flush=True)
+    print(json.dumps(dqn_measure(a.dqn_envs, a.dqn_mini_batch, a.warmup, a.steps, a.kernel_reps, a.dqn_gemm,
+                                 a.dump_outputs)), flush=True)
 
 
 GEMM_LABEL = {
@@ -942,6 +1017,7 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     steps_done = agent.optim_step
+    dumped = dump_outputs(a.dump_outputs, ppo_outputs(agent)) if a.dump_outputs and rank == 0 else None
     # rollout-only rate (no update) for the breakdown
     agent.args.testing = True
     iteration()
@@ -1047,6 +1123,8 @@ def main():
             "mean_episode_return": None if ep_cnt == 0 else round(ep_ret, 4),
             "mean_episode_length": None if ep_cnt == 0 else round(ep_len, 2), "episodes_finished": ep_cnt,
         }
+        if dumped:
+            line["dumped_outputs"] = dumped
         if world > 1:
             line["grad_exchange_us_per_step"] = exchange_us.get(used_exchange)   # the exchange `value` ran on
             line["grad_exchange_variants_us"] = exchange_us         # rank 0, HIP events, the exchange alone
