@@ -261,9 +261,6 @@ __device__ __forceinline__ void df_copy_image(float4* __restrict__ dst, const fl
 {
     constexpr int PER = DF_IMAGE_HALVES / 8 / THREADS;          // 12
     static_assert(PER * THREADS * 8 == DF_IMAGE_HALVES, "whole float4 per thread");
-#ifdef DF_NO_IMAGES                                             // (timing experiments only: what do the image stores cost)
-    return;
-#endif
     float4 v[PER];
 #pragma unroll
     for (int u = 0; u < PER; ++u) v[u] = src[tl + THREADS * u];

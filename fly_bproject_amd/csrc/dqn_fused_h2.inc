@@ -1,7 +1,7 @@
 // dqn_fused_h2.inc — the fused DQN update (dqn_fused.inc: reference UselessFiles/dqn.py:64-85 in two persistent launches) in the fp16x2
 // arithmetic of mlp_fused_h2.inc: every GEMM operand is TWO fp16 terms of its scaled value (x s = h0 + h1, s a power of two per tensor
 // class), a 16-wide k block is THREE v_mfma_f32_32x32x16_f16 (h0 h0 -> `hi`; h0 h1, h1 h0 -> `lo`) instead of six bf16 products, LDS
-// plane images, weight planes and the saved H1 / dZ2 images have two planes instead of three.  Read dqn_fused.inc first: the phases,
+// plane images, weight planes and the saved H1 image have two planes instead of three.  Read dqn_fused.inc first: the phases,
 // the k-step orders (H2GemmHost MODE 1 / 2), the guests in the MFMA gaps and the register-resident dW1 / dW3 are the same; this file
 // restates them on two planes with scaled epilogues.
 //
@@ -38,7 +38,7 @@ constexpr int DH_OFF_F32 = DH_OFF_XS2 + DF_XS_HALVES;
 // fp32 tail: online b1 s_h1 | b2 s_h2 | b3, the same of the target network, row loss, scale table (48), running maxima [5][256]
 constexpr int DH_TAIL_FLOATS = 2 * DF_BIAS + BM + H2_FSC_FLOATS + DH_NMAX * THREADS;
 constexpr int DH_LDS_BYTES = DH_OFF_F32 * 2 + DH_TAIL_FLOATS * 4;
-constexpr int DH_IMAGE_HALVES = 2 * BM * FS_P1;                          // one saved image (H1 or dZ2) of a tile: 16384 16-bit words
+constexpr int DH_IMAGE_HALVES = 2 * BM * FS_P1;                          // one image slot of a tile (H1's planes | dZ2's record): 16384 16-bit words
 static_assert(DH_LDS_BYTES <= 160 * 1024 && (DH_OFF_XS * 2) % 16 == 0 && (DH_OFF_XS2 * 2) % 16 == 0 && (DH_OFF_F32 * 2) % 16 == 0,
               "fits one CU, 16-byte aligned regions");
 
@@ -299,11 +299,11 @@ __global__ __launch_bounds__(THREADS, 1) void dqn_chain_h2_kernel(
     const float* __restrict__ P, const u16* __restrict__ QH, const u16* __restrict__ QTH, const float* __restrict__ P_tgt,
     const u16* __restrict__ QH_tgt, const float* __restrict__ fsc, const DqnChunk* __restrict__ chunks, int S, long tiles_per,
     float discount, float inv_B, u16* __restrict__ images, float* __restrict__ ws1, float* __restrict__ ws2, float* __restrict__ ws3,
-    float* __restrict__ wsmax, float* __restrict__ loss_part, unsigned long long* __restrict__ stamps, int dma, int recon)
+    float* __restrict__ wsmax, float* __restrict__ loss_part, unsigned long long* __restrict__ stamps, int dma)
 {
-    // recon != 0: dZ2's plane image does not leave (dqn_dw2r_h2_kernel rebuilds dZ2 from what a row of it IS: dq[r] W3[a_r, :] with
-    // LeakyReLU's factor per column); in its place a 2304-byte record per tile -- float dq[r] s_z2 [32] | int a_r [32] | the flags
-    // unsigned [8 column tiles][64 lanes of the dZ2 epilogue] (DhDlreluOps::negmask)
+    // dZ2's plane image does not leave (dqn_dw2r_h2_kernel rebuilds dZ2 from what a row of it IS: dq[r] W3[a_r, :] with LeakyReLU's
+    // factor per column); in its place a 2304-byte record per tile in the second image slot -- float dq[r] s_z2 [32] | int a_r [32] |
+    // the flags unsigned [8 column tiles][64 lanes of the dZ2 epilogue] (DhDlreluOps::negmask)
     extern __shared__ __attribute__((aligned(16))) u16 dh_lds[];
     const DhLds L(dh_lds);
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -440,11 +440,9 @@ __global__ __launch_bounds__(THREADS, 1) void dqn_chain_h2_kernel(
             h2_store4<FS_P4>(L.Z3, lrow, 4 * lq, d, unused);
             if (lq == 0) {
                 L.rowloss[lrow] = hub;
-                if (recon) {
-                    float* rec = reinterpret_cast<float*>(images + tile * (2L * DH_IMAGE_HALVES) + DH_IMAGE_HALVES);
-                    rec[lrow] = (inv_B * fminf(fmaxf(dv, -1.0f), 1.0f)) * sc[DHC_Z2];
-                    reinterpret_cast<int*>(rec)[BM + lrow] = idx;
-                }
+                float* rec = reinterpret_cast<float*>(images + tile * (2L * DH_IMAGE_HALVES) + DH_IMAGE_HALVES);
+                rec[lrow] = (inv_B * fminf(fmaxf(dv, -1.0f), 1.0f)) * sc[DHC_Z2];
+                reinterpret_cast<int*>(rec)[BM + lrow] = idx;
             }
         }
         __syncthreads();
@@ -460,7 +458,7 @@ __global__ __launch_bounds__(THREADS, 1) void dqn_chain_h2_kernel(
         fs_tr_init<FS_P4>(tr4, lane);
         WeightHead2 wt2a, wt2b;
         h2_gemm_prefetch<DQN_H>(wt2a, QTH + DH_OFF_QTH2, 2 * wave, lane);          // dA1's first head: a phase ahead
-        // H1's plane image (32 KB) leaves as it lies: the 256 x 256 layer's weight gradient is formed from it by dqn_dw2_h2_kernel
+        // H1's plane image (32 KB) leaves as it lies: the 256 x 256 layer's weight gradient is formed from it by dqn_dw2r_h2_kernel
         dh_copy_image(reinterpret_cast<float4*>(images + tile * (2L * DH_IMAGE_HALVES)), reinterpret_cast<const float4*>(L.H1), tl);
         f32x16 hi0, lo0, hi, lo;
         const f16x8 ones = h2_ones();
@@ -488,7 +486,7 @@ __global__ __launch_bounds__(THREADS, 1) void dqn_chain_h2_kernel(
                 h2_dw_host<6, 12>(aW3[1], zf[0], af[1][0], e);
                 h2_dw_host<9, 12>(aW3[1], zf[1], af[1][1], e);
                 amz2 = fmaxf(amz2, e.am);
-                if (recon) reinterpret_cast<unsigned*>(images + tile * (2L * DH_IMAGE_HALVES) + DH_IMAGE_HALVES)[2 * BM + (2 * wave) * 64 + lane] = e.negmask;
+                reinterpret_cast<unsigned*>(images + tile * (2L * DH_IMAGE_HALVES) + DH_IMAGE_HALVES)[2 * BM + (2 * wave) * 64 + lane] = e.negmask;
             }
             // db3 (wave 0) and db2 of this wave's first column tile: column sums through an all-ones operand (small term first)
             if (wave == 0) {
@@ -514,7 +512,7 @@ __global__ __launch_bounds__(THREADS, 1) void dqn_chain_h2_kernel(
                 DhDlreluOps<FS_P1> e(hi, lo, 64 * wave + 32, L.H2, lane, q2);
                 h2_gemm_host<DQN_H, FS_P1, true, true, 2, 24, 1>(wt2a, QTH + DH_OFF_QTH2, ct0, L.H2, 0, hi0, lo0, lane, e);
                 amz2 = fmaxf(amz2, e.am);
-                if (recon) reinterpret_cast<unsigned*>(images + tile * (2L * DH_IMAGE_HALVES) + DH_IMAGE_HALVES)[2 * BM + (2 * wave + 1) * 64 + lane] = e.negmask;
+                reinterpret_cast<unsigned*>(images + tile * (2L * DH_IMAGE_HALVES) + DH_IMAGE_HALVES)[2 * BM + (2 * wave + 1) * 64 + lane] = e.negmask;
             }
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
@@ -538,12 +536,8 @@ __global__ __launch_bounds__(THREADS, 1) void dqn_chain_h2_kernel(
                 amz1 = fmaxf(amz1, e0.am);
             }
             // the next tile's rows (requested ~15k cycles ago) have landed: nothing younger than them is in flight HERE (the weight rings
-            // were consumed, H1's image left at the top of the backward pass), so this wait is free -- behind dZ2's image it would not be
+            // were consumed, H1's image left at the top of the backward pass), so this wait is free
             fs_dma_drain();
-            // dZ2's plane image (the other 32 KB the 256 x 256 layer's weight gradient needs): the stores drain under dW1's 36 MFMAs
-            if (!recon)
-                dh_copy_image(reinterpret_cast<float4*>(images + tile * (2L * DH_IMAGE_HALVES) + DH_IMAGE_HALVES),
-                              reinterpret_cast<const float4*>(L.H2), tl);
             {
                 DhDz1Ops e1(hi, lo, hw1, zw1, q1);
                 const f16x8 z0[2] = {__builtin_bit_cast(f16x8, zw0[0][0]), __builtin_bit_cast(f16x8, zw0[0][1])};
@@ -635,9 +629,12 @@ __global__ __launch_bounds__(THREADS, 1) void dqn_chain_h2_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// dW2 = dZ2^T H1 over all tiles of the update from the saved two-plane images (dqn_dw2_kernel); the slab leaves unscaled.
-constexpr int DW2H_BUF = 2 * 2 * DW2_PLANE;                               // [H1 | dZ2][2 planes][16 rows][256]: 16384 words = 32 KB
-constexpr int DW2H_LDS_BYTES = 2 * DW2H_BUF * 2;
+// dW2 = dZ2^T H1 over all tiles of the update (dqn_dw2_kernel) without dZ2's image: a row of dZ2 is dq[r] W3[a_r, :] with LeakyReLU'
+// per column, so a k-step is H1's half image (16 KB by LDS-DMA) + the tile's 2304-byte record, and the kernel rebuilds its dZ2^T
+// fragments in registers: per element one read of the W3 table (fp32 master rows, in LDS), a multiply by dq[r] s_z2, the flag's factor,
+// then the two-term split -- in the fragment order of dw2h_frag (lane = column, elements 0 .. 3 = rows 4 hh .. + 3, 4 .. 7 = rows
+// 8 + 4 hh .. + 3 of the 16-row k-step).  The slab leaves unscaled.
+// The fragment of a 16-row half image of H1:
 __device__ __forceinline__ void dw2h_frag(f16x8 (&f)[2], const u16* half0, const FsTr& t, int T)
 {
     typedef __attribute__((address_space(3))) s16x4* lds_ptr;
@@ -654,86 +651,15 @@ __device__ __forceinline__ void dw2h_frag(f16x8 (&f)[2], const u16* half0, const
     }
 }
 
-__global__ __launch_bounds__(THREADS, 1) void dqn_dw2_h2_kernel(const u16* __restrict__ images, long ntiles, const float* __restrict__ fsc,
-                                                                  float* __restrict__ ws2)
-{
-    extern __shared__ __attribute__((aligned(16))) u16 dwh_lds[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nt0 = 4 * (wave >> 1), kt0 = 4 * (wave & 1);
-    f32x16 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 16; ++i)
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) acc[a][b][i] = 0.0f;
-    FsTr tr1;
-    fs_tr_init<FS_P1>(tr1, lane);
-    typedef __attribute__((address_space(3))) void* lptr_t;
-    const unsigned lds0 = (unsigned)(unsigned long)(lptr_t)dwh_lds;
-    const long my_tiles = blockIdx.x < ntiles ? (ntiles - blockIdx.x + gridDim.x - 1) / gridDim.x : 0;
-    const long steps = 2 * my_tiles;
-    // one k-step = 4 pieces of 8 KB (tensor T in {H1, dZ2}, plane p): 32 wave-instructions of 1 KB, eight per wave
-    auto fetch = [&](long j, int buf) {
-        const long tile = blockIdx.x + (j >> 1) * gridDim.x;
-        const u16* src = images + tile * (2L * DH_IMAGE_HALVES) + (j & 1) * DW2_PLANE;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int piece = 8 * wave + i, tp = piece >> 3, sub = piece & 7;      // tp = T * 2 + p
-            const u16* g = src + (long)tp * (2 * DW2_PLANE) + sub * 512 + lane * 8;       // images keep 32 rows per plane: stride 2 halves
-            const unsigned dst = lds0 + 2u * (unsigned)(buf * DW2H_BUF + tp * DW2_PLANE + sub * 512);
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "s"(dst), "v"(g) : "memory", "scc");
-        }
-    };
-    if (steps > 0) fetch(0, 0);
-    for (long j = 0; j < steps; ++j) {
-        const int buf = (int)(j & 1);
-        fs_dma_drain();
-        __syncthreads();
-        if (j + 1 < steps) fetch(j + 1, buf ^ 1);
-        const u16* hb = dwh_lds + buf * DW2H_BUF;                               // H1 half image
-        const u16* zb = hb + 2 * DW2_PLANE;                                     // dZ2 half image
-        f16x8 zf[2][2], af[4][2];
-#pragma unroll
-        for (int b = 0; b < 4; ++b) dw2h_frag(af[b], hb, tr1, kt0 + b);
-        dw2h_frag(zf[0], zb, tr1, nt0);
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            if (a + 1 < 4) dw2h_frag(zf[(a + 1) & 1], zb, tr1, nt0 + a + 1);
-#pragma unroll
-            for (int b = 0; b < 4; ++b) h2_dw(acc[a][b], zf[a & 1], af[b]);
-        }
-    }
-    const float u2 = fsc[H2_FSC_INV + DHC_Z2] * fsc[H2_FSC_INV + DHC_H1];
-    float* o2 = ws2 + (long)blockIdx.x * DF_STRIDE2;
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg)
-                o2[((nt0 + a) * 32 + acc_row(reg, lane)) * DQN_H + (kt0 + b) * 32 + (lane & 31)] = acc[a][b][reg] * u2;
-}
-
-// The same product without dZ2's image (recon): a row of dZ2 is dq[r] W3[a_r, :] with LeakyReLU' per column, so a k-step is H1's half image
-// (16 KB by LDS-DMA) + the tile's 2304-byte record, and this kernel rebuilds its dZ2^T fragments in registers: per element one read of
-// the W3 table (fp32 master rows, in LDS), a multiply by dq[r] s_z2, the flag's factor, then the two-term split -- in the fragment order
-// of dw2h_frag (lane = column, elements 0 .. 3 = rows 4 hh .. + 3, 4 .. 7 = rows 8 + 4 hh .. + 3 of the 16-row k-step).
 constexpr int DW2R_REC_BYTES = 2 * BM * 4 + 8 * 64 * 4;                  // 2304
 constexpr int DW2R_BUF_BYTES = 2 * DW2_PLANE * 2 + DW2R_REC_BYTES;        // 16384 + 2304
 constexpr int DW2R_W3_FLOATS = DQN_NACT * DQN_H;
-// DW2R_STAGE 0 (the product): a k-step's bytes arrive by LDS-DMA, five pieces per wave, four k-steps in LDS, counted waits.
-// 1 (-DDW2R_STAGE=1, an A/B that lost: 2.91 against 1.79 ms, DESIGN.md section 8b): they travel through registers (five 16-byte loads per
-// thread, three k-steps in flight, written to LDS at the top of their k-step) -- a DMA piece costs 0.1 - 0.2k cycles of issue beside
-// MFMAs and a plain load + ds_write_b128 a quarter of that, but beside 256 accumulator registers and eight H1 fragments the 60-register
-// staging ring spills (7 registers, 272 B of scratch per lane).
-#ifndef DW2R_STAGE
-#define DW2R_STAGE 0
-#endif
-constexpr int DW2R_NBUF = DW2R_STAGE ? 2 : 4;
-constexpr int DW2R_LDS_BYTES = DW2R_NBUF * DW2R_BUF_BYTES + DW2R_W3_FLOATS * 4 + 1024;   // (+ a dump slot: the DMA form's fetch)
+// A k-step's bytes arrive by LDS-DMA, five pieces per wave, four k-steps in LDS, counted waits.  (A/B: staged through registers instead,
+// three k-steps in flight, 2.91 against 1.79 ms, DESIGN.md section 8b -- a DMA piece costs 0.1 - 0.2k cycles of issue beside MFMAs and a
+// plain load + ds_write_b128 a quarter of that, but beside 256 accumulator registers and eight H1 fragments the 60-register staging
+// ring spills (7 registers, 272 B of scratch per lane); not kept.)
+constexpr int DW2R_NBUF = 4;
+constexpr int DW2R_LDS_BYTES = DW2R_NBUF * DW2R_BUF_BYTES + DW2R_W3_FLOATS * 4 + 1024;   // (+ a dump slot: the fetch's fifth piece of wave 3)
 
 __global__ __launch_bounds__(THREADS, 1) void dqn_dw2r_h2_kernel(const u16* __restrict__ images, long ntiles, const float* __restrict__ P,
                                                                    const float* __restrict__ fsc, float* __restrict__ ws2)
@@ -806,42 +732,6 @@ __global__ __launch_bounds__(THREADS, 1) void dqn_dw2r_h2_kernel(const u16* __re
 #pragma unroll
             for (int b = 0; b < 8; ++b) h2_dw(acc[a][b], zf[a], af[b]);
     };
-#if DW2R_STAGE
-    float4 st[3][5];
-    const int rpiece = tid < DW2R_REC_BYTES / 16 ? tid : DW2R_REC_BYTES / 16 - 1;      // (every thread loads a record piece: no branch around a load)
-    auto issue = [&](long j, auto slot) {                 // k-step j's bytes -> registers
-        constexpr int S = decltype(slot)::value;
-        const long tile = blockIdx.x + (j >> 1) * gridDim.x;
-        const u16* src = images + tile * (2L * DH_IMAGE_HALVES) + (j & 1) * DW2_PLANE;
-#pragma unroll
-        for (int u = 0; u < 4; ++u)     // 16-byte pieces tid, tid + 256 of plane 0's 8 KB, the same of plane 1's
-            st[S][u] = *reinterpret_cast<const float4*>(src + (long)(u >> 1) * (2 * DW2_PLANE) + ((u & 1) * THREADS + tid) * 8);
-        st[S][4] = *reinterpret_cast<const float4*>(images + tile * (2L * DH_IMAGE_HALVES) + DH_IMAGE_HALVES + rpiece * 8);
-    };
-    auto step = [&](long j, auto slot) {
-        constexpr int S = decltype(slot)::value;
-        const int buf = (int)(j & 1);
-        // registers -> this k-step's LDS buffer (read out two barriers ago; the compiler waits for exactly these loads)
-        float4* dstp = reinterpret_cast<float4*>(dwr_lds + buf * DW2R_BUF_BYTES);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) dstp[(u >> 1) * (DW2_PLANE / 8) + (u & 1) * THREADS + tid] = st[S][u];
-        if (tid < DW2R_REC_BYTES / 16) dstp[2 * (DW2_PLANE / 8) + tid] = st[S][4];
-        __syncthreads();                                  // k-step j is in LDS for everybody (the W3 table too, the first time)
-        if (j + 3 < steps) issue(j + 3, slot);
-        products(j, buf);
-    };
-    typedef std::integral_constant<int, 0> S0;
-    typedef std::integral_constant<int, 1> S1;
-    typedef std::integral_constant<int, 2> S2;
-    if (steps > 0) issue(0, S0{});
-    if (steps > 1) issue(1, S1{});
-    if (steps > 2) issue(2, S2{});
-    for (long j = 0; j < steps; j += 3) {
-        step(j, S0{});
-        if (j + 1 < steps) step(j + 1, S1{});
-        if (j + 2 < steps) step(j + 2, S2{});
-    }
-#else
     typedef __attribute__((address_space(3))) void* lptr_t;
     const unsigned lds0 = (unsigned)(unsigned long)(lptr_t)dwr_lds;
     // one k-step: H1's half image = 2 planes x 8 pieces of 1 KB (16 wave-instructions, four per wave) + the record (144 16-byte pieces:
@@ -884,7 +774,6 @@ __global__ __launch_bounds__(THREADS, 1) void dqn_dw2r_h2_kernel(const u16* __re
         if (j + DW2R_NBUF - 1 < steps) fetch(j + DW2R_NBUF - 1, (int)((j + DW2R_NBUF - 1) % DW2R_NBUF));
         products(j, buf);
     }
-#endif
     const float u2 = fsc[H2_FSC_INV + DHC_Z2] * fsc[H2_FSC_INV + DHC_H1];
     float* o2 = ws2 + (long)blockIdx.x * DF_STRIDE2;
 #pragma unroll

@@ -7,13 +7,10 @@
 // 73 block sums in the same order and so derives the same clip coefficient.  The step counter
 // lives in device memory (incremented by the first launch), so both are graph-capturable.
 // (round 5 A/B, rocprof in the optimizer loop: 1024-thread blocks 5.6 us, 256-thread blocks 6.15 us -- more blocks re-add the norm
-//  partials and ramp up; 1024 stays.  -DADAM_THREADS_AB=256 rebuilds the other arm.)
-#ifndef ADAM_THREADS_AB
-#define ADAM_THREADS_AB 1024
-#endif
-constexpr int ADAM_THREADS = ADAM_THREADS_AB;
+//  partials and ramp up; not kept.)
+constexpr int ADAM_THREADS = 1024;
 constexpr int ADAM_WAVES = ADAM_THREADS / 64;
-constexpr int ADAM_BLOCKS = (MLP_PACKED_FLOATS + ADAM_THREADS - 1) / ADAM_THREADS;   // 291
+constexpr int ADAM_BLOCKS = (MLP_PACKED_FLOATS + ADAM_THREADS - 1) / ADAM_THREADS;   // 73
 
 __global__ __launch_bounds__(ADAM_THREADS) void mlp_adam_norm_kernel(const float* __restrict__ G,
                                                                      const float* __restrict__ mask, float grad_scale,

@@ -386,10 +386,7 @@ __global__ __launch_bounds__(THREADS, B3 ? 3 : WGS_PER_CU) void mlp_fwd_bwd_kern
     float* __restrict__ loss_part, int* __restrict__ flags, int epoch, int* __restrict__ err,
     unsigned long long* __restrict__ stamps, int consumer_shift)
 {
-#ifndef FB_EXTRA_LDS_FLOATS
-#define FB_EXTRA_LDS_FLOATS 0
-#endif
-    __shared__ __attribute__((aligned(16))) float lds[(B3 ? FB_B3_LDS_FLOATS : FB_LDS_FLOATS) + FB_EXTRA_LDS_FLOATS];
+    __shared__ __attribute__((aligned(16))) float lds[B3 ? FB_B3_LDS_FLOATS : FB_LDS_FLOATS];
     // bf16x3: the consumer's wait result lives in the arena's last word, past everything the backward
     // body uses (a separate word would push the allocation over a third of the CU's LDS)
     static_assert(FB_B3_LDS_FLOATS > BW_B3_LDS_FLOATS, "room for the flag word");

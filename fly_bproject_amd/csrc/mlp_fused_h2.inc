@@ -24,13 +24,6 @@
 // (read that file first); this file restates the kernel on two planes, three products and scaled epilogues.  With two planes the
 // LDS image is 128 KB: the staging block of the next tile's rows gets a region of its own.
 #include "fs_h2.inc"
-// 1: layer 1's epilogues ride in MFMA gaps (dqn_fused.inc's scheme) -- column tile a's in tile b's GEMM, tile b's in the first half of
-// layer 2's GEMM, whose k-steps are ordered so that the half reads tile-a columns of H1 only (H2GemmHost MODE 1, one barrier between the
-// halves); 0: both stand exposed in front of the barrier (the first version; layer 2 as two K = 128 GEMMs in natural k order)
-#ifndef FS_H2_HOST_FWD
-#define FS_H2_HOST_FWD 1
-#endif
-
 
 // weight planes (16-bit words): the layout of PB / PTB (mlp_layout.h) with two terms per k block -- a block is 1024 words, not 1536
 constexpr int H2_OFF_PH1 = 0, H2_OFF_PH2 = H2_OFF_PH1 + 2 * MLP_H1 * MLP_IN_PAD, H2_OFF_PH3 = H2_OFF_PH2 + 2 * MLP_H2 * MLP_H1,
@@ -56,34 +49,10 @@ constexpr int H2_TAIL_FLOATS = MLP_H1 + MLP_H2 + MLP_H3 + MLP_OUT + 2 * BM + 2 *
 constexpr int H2_LDS_BYTES = H2_OFF_F32 * 2 + H2_TAIL_FLOATS * 4;
 static_assert(H2_LDS_BYTES <= 160 * 1024 && (H2_OFF_XS * 2) % 16 == 0 && (H2_OFF_F32 * 2) % 16 == 0, "fits one CU, 16-byte aligned regions");
 
-// bias + ELU epilogue (lane = row): y = ELU((hi + lo) k + bias) -- k = 1 / (s_w s_a) -- then y s -> the next GEMM's planes
-template <int PITCH, bool DUMP>
-__device__ __forceinline__ void h2_epilogue_elu(const f32x16& hi, const f32x16& lo, const float* bias, int col0, u16* plane0, int lane,
-                                                float* __restrict__ dump_tile, int nvalid, float k, float s, float& am)
-{
-    const int r = lane & 31;
-    float4 y[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const int nb = col0 + acc_n(g, lane);
-        const float4 bv = *reinterpret_cast<const float4*>(bias + nb);
-        y[g].x = elu(fmaf(hi[4 * g + 0] + lo[4 * g + 0], k, bv.x));
-        y[g].y = elu(fmaf(hi[4 * g + 1] + lo[4 * g + 1], k, bv.y));
-        y[g].z = elu(fmaf(hi[4 * g + 2] + lo[4 * g + 2], k, bv.z));
-        y[g].w = elu(fmaf(hi[4 * g + 3] + lo[4 * g + 3], k, bv.w));
-        h2_store4<PITCH>(plane0, r, nb, make_float4(y[g].x * s, y[g].y * s, y[g].z * s, y[g].w * s), am);
-    }
-    if (DUMP && dump_tile != nullptr && r < nvalid) {
-        const int go = (col0 / 32) * 1024 + lane * 4;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) GSTORE4(dump_tile + go + g * 256, y[g]);
-    }
-}
-
-// The same epilogue as single-instruction ops of four interleaved chains (dqn_fused_h2.inc's DhLreluOps with two groups at a time), for the gaps of the NEXT GEMM
-// (FS_H2_HOST_FWD): bit for bit h2_epilogue_elu's values -- t = fma(hi + lo, k s, bias s) is s times the unscaled pre-activation (powers
-// of two commute with every rounding), exp(x) as v_exp_f32 of x log2(e) with the 1 / s folded into the constant, (e - 1) s in one fma.
-// `bias_s` = the bias times s (made once per launch).
+// bias + ELU epilogue (lane = row): y = ELU((hi + lo) k + bias) -- k = 1 / (s_w s_a) -- then y s -> the next GEMM's planes, as
+// single-instruction ops of four interleaved chains (dqn_fused_h2.inc's DhLreluOps with two groups at a time), for the gaps of the NEXT
+// GEMM: t = fma(hi + lo, k s, bias s) is s times the unscaled pre-activation (powers of two commute with every rounding), exp(x) as
+// v_exp_f32 of x log2(e) with the 1 / s folded into the constant, (e - 1) s in one fma.  `bias_s` = the bias times s (made once per launch).
 template <int PITCH, bool DUMP>
 struct H2EluOps {
     static constexpr int HEAD_OPS = 12, CH = HEAD_OPS + H2_SPLIT_OPS;     // 17 ops per chain
@@ -247,7 +216,6 @@ struct H2Dz1Ops {
 template <unsigned GC>
 __device__ __forceinline__ unsigned h2_slab_bytes(unsigned lbase, unsigned G, unsigned wg, unsigned p)
 {
-    static_assert(FS_SLAB_CHUNKED, "the fp16x2 step writes chunked slabs");
     if (GC != 0) return (lbase + ((p >> 8) * GC << 8) + (wg << 8) + (p & 255u)) << 2;
     return (lbase + (((p >> 8) * G + wg) << 8) + (p & 255u)) << 2;
 }
@@ -369,9 +337,9 @@ __global__ __launch_bounds__(THREADS, 1) void mlp_fused_step_h2_kernel(
         if (tid == 0) c_hld[0] = hld;
         sc[tid] = fsc[tid];
     }
-    bias1[tid] = FS_H2_HOST_FWD ? P[MLP_OFF_B1 + tid] * fsc[H2C_H1] : P[MLP_OFF_B1 + tid];      // (hosted epilogues add the bias times s)
-    if (tid < MLP_H2) bias2[tid] = FS_H2_HOST_FWD ? P[MLP_OFF_B2 + tid] * fsc[H2C_H2] : P[MLP_OFF_B2 + tid];
-    else bias3[tid - MLP_H2] = FS_H2_HOST_FWD ? P[MLP_OFF_B3 + tid - MLP_H2] * fsc[H2C_H3] : P[MLP_OFF_B3 + tid - MLP_H2];
+    bias1[tid] = P[MLP_OFF_B1 + tid] * fsc[H2C_H1];                      // (the epilogues add the bias times s)
+    if (tid < MLP_H2) bias2[tid] = P[MLP_OFF_B2 + tid] * fsc[H2C_H2];
+    else bias3[tid - MLP_H2] = P[MLP_OFF_B3 + tid - MLP_H2] * fsc[H2C_H3];
     if (tid < MLP_OUT) bias4[tid] = P[MLP_OFF_B4 + tid];
 #pragma unroll
     for (int c = 0; c < H2_NACT_CLASSES; ++c) amax[c * THREADS + tid] = 0.0f;
@@ -431,8 +399,9 @@ __global__ __launch_bounds__(THREADS, 1) void mlp_fused_step_h2_kernel(
             const float k1 = sc[H2_FSC_INV + H2C_X] * sc[H2_FSC_INV + H2C_W1], s1 = sc[H2C_H1];
             const float k2 = sc[H2_FSC_INV + H2C_H1] * sc[H2_FSC_INV + H2C_W2], s2 = sc[H2C_H2];
             WeightHead2 w3;
-#if FS_H2_HOST_FWD
-            {
+            {   // layer 1's epilogues ride in MFMA gaps (dqn_fused.inc's scheme) -- column tile a's in tile b's GEMM, tile b's in the first
+                // half of layer 2's GEMM, whose k-steps are ordered so that the half reads tile-a columns of H1 only (H2GemmHost MODE 1,
+                // one barrier between the halves)
                 f32x16 hi0, lo0;
                 const float is1 = sc[H2_FSC_INV + H2C_H1];
                 h2_gemm_prefetch<MLP_IN_PAD>(w1b, PH + H2_OFF_PH1, 2 * wave + 1, lane);
@@ -459,38 +428,13 @@ __global__ __launch_bounds__(THREADS, 1) void mlp_fused_step_h2_kernel(
             }
             h2_gemm_prefetch<MLP_H2>(w3, PH + H2_OFF_PH3, wave, lane);
             am = 0.0f;
-#else
-            h2_gemm<MLP_IN_PAD, FS_PX, false>(w1, PH + H2_OFF_PH1, 2 * wave, Xc, 0, hi, lo, lane);
-            h2_gemm_prefetch<MLP_IN_PAD>(w1b, PH + H2_OFF_PH1, 2 * wave + 1, lane);
-            h2_epilogue_elu<FS_P1, DUMP>(hi, lo, bias1, 64 * wave, H1, lane, d_h1, nvalid, k1, s1, am);
-            h2_gemm<MLP_IN_PAD, FS_PX, false>(w1b, PH + H2_OFF_PH1, 2 * wave + 1, Xc, 0, hi, lo, lane);
-            h2_gemm_prefetch<MLP_H2>(w2a, PH + H2_OFF_PH2, wave, lane);
-            h2_epilogue_elu<FS_P1, DUMP>(hi, lo, bias1, 64 * wave + 32, H1, lane, d_h1, nvalid, k1, s1, am);
-            h2_amax_fold(amax, H2C_H1, tl, am);
-            stamp<STAMP>(stamps, 2);
-            if (!STAMP) fs_split(n);
-            __syncthreads();
-            stamp<STAMP>(stamps, 3);
-            if (!STAMP) fs_split(n);
-            // ---- P2: layer 2 (K = 256 as two K = 128 operands) ----------------------------------------------------------
-            WeightHead2 w2b;
-            h2_gemm_prefetch<MLP_H2>(w2b, PH + H2_OFF_PH2 + 2 * MLP_H2 * (MLP_H1 / 2), wave, lane);
-            h2_gemm<MLP_H2, FS_P1, false>(w2a, PH + H2_OFF_PH2, wave, H1, 0, hi, lo, lane);
-            h2_gemm<MLP_H2, FS_P1, false, false>(w2b, PH + H2_OFF_PH2 + 2 * MLP_H2 * (MLP_H1 / 2), wave, H1, MLP_H1 / 2, hi, lo, lane);
-            h2_gemm_prefetch<MLP_H2>(w3, PH + H2_OFF_PH3, wave, lane);
-            am = 0.0f;
-#endif
-#if FS_H2_HOST_FWD      // (exposed, but as the pinned ops of four interleaved chains: the loop form is one dependent chain per pair of outputs)
-            {
+            {   // (exposed, but as the pinned ops of four interleaved chains: the loop form is one dependent chain per pair of outputs)
                 H2EluOps<FS_P2, DUMP> e(hi, lo, bias2, 32 * wave, H2, lane, d_h2, nvalid, k2, s2, sc[H2_FSC_INV + H2C_H2]);
                 __builtin_amdgcn_sched_barrier(0);
                 fs_run_ops<0, H2EluOps<FS_P2, DUMP>::TOTAL>(e);
                 __builtin_amdgcn_sched_barrier(0);
                 am = e.am;
             }
-#else
-            h2_epilogue_elu<FS_P2, DUMP>(hi, lo, bias2, 32 * wave, H2, lane, d_h2, nvalid, k2, s2, am);
-#endif
             h2_amax_fold(amax, H2C_H2, tl, am);
             __syncthreads();
             stamp<STAMP>(stamps, 4);
@@ -500,7 +444,6 @@ __global__ __launch_bounds__(THREADS, 1) void mlp_fused_step_h2_kernel(
             h2_gemm_prefetch<32>(w4, PH + H2_OFF_PH4 + (long)(2 * wave) * 1024, 0, lane);
             h2_gemm<MLP_H2, FS_P2, false>(w3, PH + H2_OFF_PH3, wave, H2, 0, hi, lo, lane);
             am = 0.0f;
-#if FS_H2_HOST_FWD
             {
                 H2EluOps<FS_P2, DUMP> e(hi, lo, bias3, 32 * wave, H3, lane, d_h3, nvalid, k3, s3, sc[H2_FSC_INV + H2C_H3]);
                 __builtin_amdgcn_sched_barrier(0);
@@ -508,9 +451,6 @@ __global__ __launch_bounds__(THREADS, 1) void mlp_fused_step_h2_kernel(
                 __builtin_amdgcn_sched_barrier(0);
                 am = e.am;
             }
-#else
-            h2_epilogue_elu<FS_P2, DUMP>(hi, lo, bias3, 32 * wave, H3, lane, d_h3, nvalid, k3, s3, am);
-#endif
             h2_amax_fold(amax, H2C_H3, tl, am);
             // (no barrier: H3's columns 32 w .. 32 w + 31 are only ever read by the wave that wrote them -- layer 4's split-K range,
             //  dW4's operand and the dZ3 epilogue of wave w are exactly these columns -- and a wave's LDS operations complete in order)

@@ -25,13 +25,6 @@
 // that holds the two paths together.  dW differs from mlp_grad_w_b3 only in summation order (per-CU tile sets
 // instead of row slabs).
 #include "fs_common.inc"
-#ifndef FS_LATE_DRAIN
-#define FS_LATE_DRAIN 0     // 1: the next tile's LDS-DMA is drained only before the SECOND column tile's dW1, which then hosts the whole
-                            // conversion.  Measured neutral (125.8 vs 126.0 us, same box): the drain is not what column tile 0's dW2 waits for
-#endif
-#ifndef FS_ZSUM_LATE
-#define FS_ZSUM_LATE 1      // db1's running sum: pair sums formed beside the split, added in the lightest MFMA gap (A/B: 0 = in the dact gap)
-#endif
 // LDS regions and who lives in them when (P0 .. P8 = the phases of a tile):
 //   X   2 x [32][96] x 3 planes  the tile's input rows (P1 .. P8) and, in the other buffer, the NEXT tile's: converted from the staging block
 //                             in the MFMA gaps of this tile's last dW1 product (which reads the current buffer)
@@ -218,35 +211,32 @@ struct FsDz1Ops {
             if (j == 5) zq[s][1][m] = ch.b;
             if (j == 10) zq[s][2][m] = ch.c;
         }
+        // db1's running sum: the pair sum formed beside the split, added in the lightest MFMA gap (A/B: in the dact gap; not kept)
         if (i == 17 + FS_SPLIT_OPS) { zsum += e.vs; fs_pin(zsum); }
     }
     // pairs 2 pp, 2 pp + 1 interleaved: ops 2 CH pp .. 2 CH (pp + 1) - 1
     __device__ __forceinline__ void q(int t) { const int pp = t / (2 * CH), o = t % (2 * CH); chain_op(2 * pp + (o & 1), o & 1, o >> 1); }
 };
 
-// Where element p of a layer's packed-gradient block lives in the partial slabs.  FS_SLAB_CHUNKED: the slabs of the `G` workgroups are
-// interleaved in 1 KiB chunks -- [chunk p >> 8][workgroup][256 floats] -- so that the reduction, whose waves each sum ONE output
-// position over all workgroups, reads a contiguous run of G KiB instead of G pieces a slab apart (strides of 66 .. 132 KB: a fixed
-// residue of the channel interleave); the burst that writes the slabs is 128-byte pieces either way.  Otherwise slab after slab.
-#ifndef FS_SLAB_CHUNKED
-#define FS_SLAB_CHUNKED 1
-#endif
+// Where element p of a layer's packed-gradient block lives in the partial slabs: the slabs of the `G` workgroups are interleaved in
+// 1 KiB chunks -- [chunk p >> 8][workgroup][256 floats] -- so that the reduction, whose waves each sum ONE output position over all
+// workgroups, reads a contiguous run of G KiB instead of G pieces a slab apart (strides of 66 .. 132 KB: a fixed residue of the
+// channel interleave); the burst that writes the slabs is 128-byte pieces either way.
 constexpr long fs_pad256(long n) { return (n + 255) / 256 * 256; }
 // float index of element p of a layer's block, relative to `ws`: 32-bit arithmetic throughout (all the slabs together are < 2^30
 // floats), so that a store is a scalar base + a 32-bit lane offset; `lbase` = where the layer's slab region starts
-__device__ __forceinline__ unsigned fs_slab(unsigned lbase, unsigned G, unsigned wg, unsigned stride, unsigned p)
+__device__ __forceinline__ unsigned fs_slab(unsigned lbase, unsigned G, unsigned wg, unsigned p)
 {
-    if (FS_SLAB_CHUNKED) return lbase + (((p >> 8) * G + wg) << 8) + (p & 255u);
-    return lbase + wg * stride + p;
+    return lbase + (((p >> 8) * G + wg) << 8) + (p & 255u);
 }
 // partial slab: tile (nt, kt) of a layer's [N][KOUT] block; lane = column k, registers = rows n
-__device__ __forceinline__ void fs_store_tile(float* __restrict__ ws, unsigned lbase, unsigned G, unsigned wg, unsigned stride, int KOUT,
+__device__ __forceinline__ void fs_store_tile(float* __restrict__ ws, unsigned lbase, unsigned G, unsigned wg, int KOUT,
                                               int nt, int kt, const f32x16& acc, int lane)
 {
     const int col = kt * 32 + (lane & 31);
     if (col < KOUT) {
 #pragma unroll
-        for (int reg = 0; reg < 16; ++reg) ws[fs_slab(lbase, G, wg, stride, (unsigned)((nt * 32 + acc_row(reg, lane)) * KOUT + col))] = acc[reg];
+        for (int reg = 0; reg < 16; ++reg) ws[fs_slab(lbase, G, wg, (unsigned)((nt * 32 + acc_row(reg, lane)) * KOUT + col))] = acc[reg];
     }
 }
 
@@ -369,10 +359,7 @@ __global__ __launch_bounds__(THREADS, 1) void mlp_fused_step_kernel(
     if (tid < MLP_H2) bias2[tid] = P[MLP_OFF_B2 + tid];
     else bias3[tid - MLP_H2] = P[MLP_OFF_B3 + tid - MLP_H2];
     if (tid < MLP_OUT) bias4[tid] = P[MLP_OFF_B4 + tid];
-#ifndef FS_EARLY_CLEAR
-#define FS_EARLY_CLEAR 1
-#endif
-    if (!STAMP && FS_EARLY_CLEAR) {
+    if (!STAMP) {
         // the 304 accumulator registers are cleared HERE, while the first tile's rows and the biases are in flight: left alone the
         // compiler sinks the clears behind the barrier, to the first use (~2k cycles of nothing but register writes per launch).
         // (Not in the diagnostic build: its stamp registers make the pins spill.)
@@ -704,20 +691,18 @@ __global__ __launch_bounds__(THREADS, 1) void mlp_fused_step_kernel(
                 if (t == 0) {
                     bs2 += fs_colsum_done(cs2);
                     // this wave's share of the next tile's rows has landed (requested ~3k cycles ago, ahead of 54 MFMAs)
-                    if (!FS_LATE_DRAIN) fs_dma_drain();
+                    // (A/B: drained only before the second column tile's dW1, which then hosts the whole conversion -- neutral,
+                    // 125.8 vs 126.0 us, same box: the drain is not what column tile 0's dW2 waits for)
+                    fs_dma_drain();
                     gemm_prefetch_b3<MLP_H2>(wt2b, PTB + MLP_OFF_PTB2, 2 * wave + 1, lane);      // lands during dW1 of tile 0
-                } else if (FS_LATE_DRAIN) {
-                    fs_dma_drain();     // this wave's share of the next tile's rows has landed (requested a GEMM and 132 MFMAs ago)
                 }
                 stamp<STAMP>(stamps, t == 0 ? 13 : 15);
                 if (!STAMP) fs_split(n);
                 {
-                    // dW1[n tile ct][k tile kt]: both k-steps back to back.  Behind the second column tile's 36 MFMAs rides the
-                    // conversion of the NEXT tile's rows (staging -> the other X buffer): granule kt behind k tile kt
-                    // (in a workgroup's LAST tile the slices convert whatever the staging block holds into a buffer nobody reads:
-                    // cheaper than a second copy of the 36 MFMAs without them)
-                    // both column tiles host it: 36 slices over 72 MFMAs, three per dW1 k-step
-                    // (a workgroup's LAST tile converts whatever the staging block holds into a buffer nobody reads)
+                    // dW1[n tile ct][k tile kt]: both k-steps back to back.  Behind the MFMAs rides the conversion of the NEXT
+                    // tile's rows (staging -> the other X buffer): both column tiles host it, 36 slices over 72 MFMAs, three per dW1
+                    // k-step (in a workgroup's LAST tile the slices convert whatever the staging block holds into a buffer nobody reads:
+                    // cheaper than a second copy of the 72 MFMAs without them)
                     bf16x8 af[2][2][3];                                    // [buffer][k-step][term]
                     fs_trns<FS_PX>(af[0][0], Xc, trx, 0, 0);
                     fs_trns<FS_PX>(af[0][1], Xc, trx, 0, 1);
@@ -728,16 +713,8 @@ __global__ __launch_bounds__(THREADS, 1) void mlp_fused_step_kernel(
                             fs_trns<FS_PX>(af[(kt + 1) & 1][1], Xc, trx, kt + 1, 1);
                         }
                         __builtin_amdgcn_sched_barrier(0);
-                        if (!FS_LATE_DRAIN) {       // both column tiles host the conversion: 36 slices over 72 MFMAs
-                            fs_dw_fill3(aW1[t][kt], z1f[0], af[kt & 1][0], xc, 18 * t + 6 * kt);
-                            fs_dw_fill3(aW1[t][kt], z1f[1], af[kt & 1][1], xc, 18 * t + 6 * kt + 3);
-                        } else if (t == 0) {
-                            fs_dw(aW1[t][kt], z1f[0], af[kt & 1][0]);
-                            fs_dw(aW1[t][kt], z1f[1], af[kt & 1][1]);
-                        } else {                    // granule kt's twelve slices behind k tile kt's twelve MFMAs
-                            fs_dw_fill(aW1[t][kt], z1f[0], af[kt & 1][0], xc, kt, 0);
-                            fs_dw_fill(aW1[t][kt], z1f[1], af[kt & 1][1], xc, kt, 6);
-                        }
+                        fs_dw_fill3(aW1[t][kt], z1f[0], af[kt & 1][0], xc, 18 * t + 6 * kt);
+                        fs_dw_fill3(aW1[t][kt], z1f[1], af[kt & 1][1], xc, 18 * t + 6 * kt + 3);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
@@ -757,33 +734,32 @@ __global__ __launch_bounds__(THREADS, 1) void mlp_fused_step_kernel(
     // ---- one partial slab per workgroup, laid out like the packed gradient (weights then biases per layer) ----------------
     const int lane = tid & 63;
     const unsigned G = gridDim.x, wg = blockIdx.x;
-    constexpr unsigned S1 = FS_SLAB_CHUNKED ? fs_pad256(FS_STRIDE1) : FS_STRIDE1, S2 = FS_SLAB_CHUNKED ? fs_pad256(FS_STRIDE2) : FS_STRIDE2,
-                       S3 = FS_SLAB_CHUNKED ? fs_pad256(FS_STRIDE3) : FS_STRIDE3;
+    constexpr unsigned S1 = fs_pad256(FS_STRIDE1), S2 = fs_pad256(FS_STRIDE2), S3 = fs_pad256(FS_STRIDE3);
     const unsigned o1 = 0, o2 = G * S1, o3 = G * (S1 + S2), o4 = G * (S1 + S2 + S3);      // the layers' slab regions (each G slabs)
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-        for (int kt = 0; kt < 3; ++kt) fs_store_tile(ws, o1, G, wg, FS_STRIDE1, MLP_IN_PAD, 2 * wave + t, kt, aW1[t][kt], lane);
+        for (int kt = 0; kt < 3; ++kt) fs_store_tile(ws, o1, G, wg, MLP_IN_PAD, 2 * wave + t, kt, aW1[t][kt], lane);
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-        for (int t = 0; t < 2; ++t) fs_store_tile(ws, o2, G, wg, FS_STRIDE2, MLP_H1, nt, 2 * wave + t, aW2[nt][t], lane);
+        for (int t = 0; t < 2; ++t) fs_store_tile(ws, o2, G, wg, MLP_H1, nt, 2 * wave + t, aW2[nt][t], lane);
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b) fs_store_tile(ws, o3, G, wg, FS_STRIDE3, MLP_H2, 2 * (wave >> 1) + a, 2 * (wave & 1) + b, aW3[a][b], lane);
-    fs_store_tile(ws, o4, G, wg, FS_STRIDE4, MLP_H3, 0, wave, aW4, lane);
+        for (int b = 0; b < 2; ++b) fs_store_tile(ws, o3, G, wg, MLP_H2, 2 * (wave >> 1) + a, 2 * (wave & 1) + b, aW3[a][b], lane);
+    fs_store_tile(ws, o4, G, wg, MLP_H3, 0, wave, aW4, lane);
     // bias gradients: lane = column (fs_colsum): db2 of column tile `wave`, db3 of tile 2 (wave >> 1) + (wave & 1) = wave, db4 (same in
     // every wave); db1 sits in the two lane halves of the swapped-role accumulators
     if (lane < 32) {
-        ws[fs_slab(o2, G, wg, FS_STRIDE2, MLP_H2 * MLP_H1 + 32 * wave + lane)] = bs2;
-        ws[fs_slab(o3, G, wg, FS_STRIDE3, MLP_H3 * MLP_H2 + 32 * wave + lane)] = bs3;
-        if (wave == 0) ws[fs_slab(o4, G, wg, FS_STRIDE4, MLP_OUT * MLP_H3 + lane)] = bs4;
+        ws[fs_slab(o2, G, wg, MLP_H2 * MLP_H1 + 32 * wave + lane)] = bs2;
+        ws[fs_slab(o3, G, wg, MLP_H3 * MLP_H2 + 32 * wave + lane)] = bs3;
+        if (wave == 0) ws[fs_slab(o4, G, wg, MLP_OUT * MLP_H3 + lane)] = bs4;
     }
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
         const float v = bs1[t] + __shfl_xor(bs1[t], 32, 64);
-        if (lane < 32) ws[fs_slab(o1, G, wg, FS_STRIDE1, MLP_H1 * MLP_IN_PAD + 32 * (2 * wave + t) + lane)] = v;
+        if (lane < 32) ws[fs_slab(o1, G, wg, MLP_H1 * MLP_IN_PAD + 32 * (2 * wave + t) + lane)] = v;
     }
     if (STAMP) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -836,11 +812,8 @@ __device__ __forceinline__ void policy_tile_fs_setup(const FrLds& L, const float
 // and every HBM row store have been issued by all waves when it returns (the stores are not waited for).
 // `w1`: the head of layer 1's first column tile (policy_tile_fs_head), requested by the caller BEFORE the env step that precedes
 // this call: the weights are the same every step, and their L2 round trip then hides under the physics.
-#ifndef FR_HEAD
-#define FR_HEAD 2           // (4 = the whole weight ring a phase ahead measured SLOWER in the same box: 22.7 vs 21.9 us per env step)
-#endif
-typedef WeightHeadT<FR_HEAD> FrHead;
-__device__ __forceinline__ void policy_tile_fs_head(FrHead& w1, const u16* __restrict__ PB)
+// (A/B: the whole weight ring a phase ahead, WeightHeadT<4>, measured SLOWER in the same box: 22.7 vs 21.9 us per env step)
+__device__ __forceinline__ void policy_tile_fs_head(WeightHeadT<2>& w1, const u16* __restrict__ PB)
 {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     gemm_prefetch_b3<MLP_IN_PAD>(w1, PB + MLP_OFF_PB1, 2 * wave, threadIdx.x & 63);
@@ -848,7 +821,7 @@ __device__ __forceinline__ void policy_tile_fs_head(FrHead& w1, const u16* __res
 template <bool STAMP = false>
 __device__ __forceinline__ void policy_tile_fs(const FrLds& L, const long tile, const u16* __restrict__ PB, const float* __restrict__ x,
                                                const long n, float* __restrict__ v_out, const float* __restrict__ smp_eps,
-                                               float* __restrict__ smp_act, float* __restrict__ smp_logp, const FrHead& w1,
+                                               float* __restrict__ smp_act, float* __restrict__ smp_logp, const WeightHeadT<2>& w1,
                                                unsigned long long* stamps = nullptr)
 {
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -889,7 +862,7 @@ __device__ __forceinline__ void policy_tile_fs(const FrLds& L, const long tile, 
     WeightHeadT<2> w4;
     {
         f32x16 hi, lo;
-        FrHead w1b, w2a;
+        WeightHeadT<2> w1b, w2a;
         fs_gemm<MLP_IN_PAD, FS_PX, false>(w1, PB + MLP_OFF_PB1, 2 * wave, L.X, 0, hi, lo, lane);
         gemm_prefetch_b3<MLP_IN_PAD>(w1b, PB + MLP_OFF_PB1, 2 * wave + 1, lane);
         fs_epilogue_elu<FS_P1, false>(hi, lo, L.bias1, 64 * wave, L.H1, lane, nullptr, nvalid);
@@ -898,7 +871,7 @@ __device__ __forceinline__ void policy_tile_fs(const FrLds& L, const long tile, 
         fs_epilogue_elu<FS_P1, false>(hi, lo, L.bias1, 64 * wave + 32, L.H1, lane, nullptr, nvalid);
         __syncthreads();
         stamp<STAMP>(stamps, 2);
-        FrHead w2b, w3;
+        WeightHeadT<2> w2b, w3;
         gemm_prefetch_b3<MLP_H2>(w2b, PB + MLP_OFF_PB2 + 3 * MLP_H2 * (MLP_H1 / 2), wave, lane);
         fs_gemm<MLP_H2, FS_P1, false>(w2a, PB + MLP_OFF_PB2, wave, L.H1, 0, hi, lo, lane);
         fs_gemm<MLP_H2, FS_P1, false, false>(w2b, PB + MLP_OFF_PB2 + 3 * MLP_H2 * (MLP_H1 / 2), wave, L.H1, MLP_H1 / 2, hi, lo, lane);

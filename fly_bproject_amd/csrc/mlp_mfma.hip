@@ -146,9 +146,6 @@ __global__ __launch_bounds__(THREADS, WPS) void rollout_all_kernel(
 // STAMP (diagnostic instantiation, bench.py / tools/ab_rollout.py): thread 0 of every workgroup stores s_memtime into stamps
 // u64 [tile][T + 1][8]: slot 0 the top of step t, 1 .. 5 inside the policy (x converted, layer 1, 2, 3, 4 done), 7 between the
 // policy and env halves (+ the 100 MHz real-time counter once, at [T][1]).
-#ifndef FR_HOIST
-#define FR_HOIST 1          // layer 1's first weights of the NEXT step are requested before the env step (A/B: 0)
-#endif
 // MULTI: more tiles than workgroups (> 8192 envs on 256 CUs): the outer loop really loops; the single-tile instantiation keeps
 // the register allocation of a kernel without it.
 template <bool STAMP, bool MULTI>
@@ -175,7 +172,7 @@ __global__ __launch_bounds__(THREADS, 1) void rollout_all_fs_kernel(
         b.reset = reset0; b.progress = progress0;
         FlyRegs st;
         fly_load<PH_ALL>(st, c, b, (int)tile);
-        FrHead w1;
+        WeightHeadT<2> w1;
         policy_tile_fs_head(w1, PB);
         __syncthreads();
         if (STAMP && threadIdx.x == 0) st_tile[6] = realtime_cu();      // (with [T][1]: the shader clock the stamps tick at)
@@ -185,11 +182,11 @@ __global__ __launch_bounds__(THREADS, 1) void rollout_all_fs_kernel(
             b.obs = obs_ring + (long)(t + 1) * n * FLY_NUM_OBS;
             b.reward = reward_all + (long)t * n;
             if (reset_rows) { b.reset = reset_rows + (long)t * n; b.progress = progress_rows + (long)t * n; }   // fly.py:175-177, per step
-            if (!FR_HOIST && t > 0) policy_tile_fs_head(w1, PB);
             policy_tile_fs<STAMP>(L, tile, PB, t == 0 ? obs_ring : nullptr, n, v_ring + (long)t * n, eps_all + (long)t * n * MLP_NACT, act,
                                   logp_all + (long)t * n, w1, STAMP ? st_tile + 8 * t : nullptr);
             stamp<STAMP>(st_tile, 8 * t + 7);
-            if (FR_HOIST) policy_tile_fs_head(w1, PB);     // the NEXT step's first weights: their round trip hides under the physics
+            policy_tile_fs_head(w1, PB);     // the NEXT step's first weights: their round trip hides under the physics (A/B: requested
+                                             // after the env step; not kept)
             FlyRegs nx;
             fly_body<PH_ALL>(c, act, b, L.obs, (int)tile, st, &nx, L.acts);
             st = nx;
@@ -525,7 +522,8 @@ extern "C" hipError_t flyhip_launch_mlp_fused_grad(const float* P, const uint16_
 #undef FS_LAUNCH
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    // the slabs have the layout the reduction already sums: per layer `grid` blocks of N*KP + N floats
+    // the slabs have the layout the reduction already sums: per layer `grid` blocks of N*KP + N floats, padded to whole 1 KiB chunks
+    // and interleaved chunk by chunk (fs_slab)
     GradWTable T;
     const int N[4] = {MLP_H1, MLP_H2, MLP_H3, MLP_OUT};
     const int KP[4] = {MLP_IN_PAD, MLP_H1, MLP_H2, MLP_H3};
@@ -533,9 +531,8 @@ extern "C" hipError_t flyhip_launch_mlp_fused_grad(const float* P, const uint16_
     for (int l = 0; l < 4; ++l) {
         T.l[l].dz = nullptr; T.l[l].a = nullptr; T.l[l].partial = w;
         T.l[l].N = N[l]; T.l[l].Ka = KP[l]; T.l[l].KP = KP[l]; T.l[l].wgs = grid; T.l[l].first_block = 0; T.l[l].accumulate = 0;
-        T.l[l].chunked = FS_SLAB_CHUNKED;
-        const long stride = (long)N[l] * KP[l] + N[l];
-        w += (long)grid * (FS_SLAB_CHUNKED ? fs_pad256(stride) : stride);
+        T.l[l].chunked = 1;
+        w += (long)grid * fs_pad256((long)N[l] * KP[l] + N[l]);
     }
     // (loads in flight per wave: 4 -> 15.8 us for the 256 slabs, 8 -> 17.2, 16 -> 58 (the 1024-thread block's register budget))
     hipLaunchKernelGGL(mlp_grad_reduce_kernel<4>, dim3(RED_BLOCKS), dim3(64 * RED_WAVES), 0, (hipStream_t)stream, T, grad_out,

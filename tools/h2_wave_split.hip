@@ -23,6 +23,25 @@ namespace {
 #include "mlp_fused_step.inc"
 #include "mlp_fused_h2.inc"
 
+// the 4-wave form's epilogue (the kernel's first, unhosted one): y = ELU((hi + lo) k + bias), then y s -> the next planes
+template <int PITCH>
+__device__ __forceinline__ void h2_epilogue_elu(const f32x16& hi, const f32x16& lo, const float* bias, int col0, u16* plane0, int lane,
+                                                float k, float s, float& am)
+{
+    const int r = lane & 31;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const int nb = col0 + acc_n(g, lane);
+        const float4 bv = *reinterpret_cast<const float4*>(bias + nb);
+        float4 y;
+        y.x = elu(fmaf(hi[4 * g + 0] + lo[4 * g + 0], k, bv.x));
+        y.y = elu(fmaf(hi[4 * g + 1] + lo[4 * g + 1], k, bv.y));
+        y.z = elu(fmaf(hi[4 * g + 2] + lo[4 * g + 2], k, bv.z));
+        y.w = elu(fmaf(hi[4 * g + 3] + lo[4 * g + 3], k, bv.w));
+        h2_store4<PITCH>(plane0, r, nb, make_float4(y.x * s, y.y * s, y.z * s, y.w * s), am);
+    }
+}
+
 constexpr int WS_LDS_HALVES = 2 * (2 * BM * FS_P1) + 2 * BM * FS_P2;        // two H1-sized plane sets (ping-pong) + one H2-sized
 constexpr int WS_XCH_FLOATS = 8 * 2 * 64 * 4;                                 // exchange: [wave][2][lane] float4
 
@@ -57,7 +76,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void phase_kernel(const u16*
             } else {
                 for (int i = 0; i < 16; ++i) { hi[i] = am + i; lo[i] = 0.001f * i; }
             }
-            if (PARTS != 1) h2_epilogue_elu<FS_P1, false>(hi, lo, bias, 32 * wave, outp, lane, nullptr, 32, k, s, am);
+            if (PARTS != 1) h2_epilogue_elu<FS_P1>(hi, lo, bias, 32 * wave, outp, lane, k, s, am);
             else am += hi[3] + lo[5];
             if (PARTS == 0 || PARTS == 3) __syncthreads();
         } else {
