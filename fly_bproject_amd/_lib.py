@@ -19,7 +19,7 @@ class FlyBuffers(C.Structure):
                                           "done_return", "done_length", "done_count")]
 
 
-ABI_VERSION = 12        # include/flyhip.h as this package binds it (fly_abi_version(): argument lists changed between versions)
+ABI_VERSION = 13        # include/flyhip.h as this package binds it (fly_abi_version(): argument lists changed between versions)
 # name -> argtypes; every entry point returns int except fly_last_error
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 SYMBOLS = {

@@ -228,7 +228,7 @@ __device__ __forceinline__ void dh_forward(const DhLds& L, const u16* X, const u
     {
         DhLreluOps<FS_P1> e(hi0, lo0, bias, 64 * wave, L.H1, lane, k1);
         h2_gemm_host<DQN_IN_PAD, FS_PX, false>(w1b, QHn + DH_OFF_QH1, 2 * wave + 1, X, 0, hi, lo, lane, e);
-        am1 = fmaxf(am1, e.am);
+        am1 = h2_nanmax(am1, e.am);
     }
     __syncthreads();                                                          // every wave's tile-a columns of H1 are stored
     df_stamp(sb, slot0 + 1);
@@ -237,17 +237,17 @@ __device__ __forceinline__ void dh_forward(const DhLds& L, const u16* X, const u
         if (XC) {
             H2XStoreOps xc(L.xs2, L.Xo, tl, sc[DHC_X]);                        // (the staged rows landed a tile ago: the caller drained)
             h2_gemm_host2<DQN_H, FS_P1, false, true, 2, 24, 1>(w2a, QHn + DH_OFF_QH2, 2 * wave, L.H1, 0, hi0, lo0, lane, e, xc);
-            amx = fmaxf(amx, xc.am);
+            amx = h2_nanmax(amx, xc.am);
         } else {
             h2_gemm_host<DQN_H, FS_P1, false, true, 2, 24, 1>(w2a, QHn + DH_OFF_QH2, 2 * wave, L.H1, 0, hi0, lo0, lane, e);
         }
-        am1 = fmaxf(am1, e.am);
+        am1 = h2_nanmax(am1, e.am);
     }
     h2_gemm_prefetch<DQN_H>(w2b, QHn + DH_OFF_QH2, 2 * wave + 1, lane);
     {
         DhLreluOps<FS_P1> e(hi0, lo0, bias + DQN_H, 64 * wave, L.H2, lane, k2);
         h2_gemm_host<DQN_H, FS_P1, false>(w2b, QHn + DH_OFF_QH2, 2 * wave + 1, L.H1, 0, hi, lo, lane, e);
-        am2 = fmaxf(am2, e.am);
+        am2 = h2_nanmax(am2, e.am);
     }
     h2_gemm_prefetch<64, 4>(w3, QHn + DH_OFF_QH3 + (long)(4 * wave) * 1024, 0, lane);     // the last layer's k range of this wave
     if (AHEAD) {
@@ -262,7 +262,7 @@ __device__ __forceinline__ void dh_forward(const DhLds& L, const u16* X, const u
     {
         DhLreluOps<FS_P1> e(hi, lo, bias + DQN_H, 64 * wave + 32, L.H2, lane, k2);
         h2_gemm_host<64, FS_P1, false, true, 4, 6, 2>(w3, QHn + DH_OFF_QH3 + (long)(4 * wave) * 1024, 0, L.H2, 64 * wave, hi0, lo0, lane, e);
-        am2 = fmaxf(am2, e.am);
+        am2 = h2_nanmax(am2, e.am);
     }
     float* pw = L.part + wave * (BM * DQN_OUT);
 #pragma unroll
@@ -359,7 +359,7 @@ __global__ __launch_bounds__(THREADS, 1) void dqn_chain_h2_kernel(
         fs_dma_drain();
         H2XStoreOps xc(L.xs, L.Xt, tid, sc[DHC_X]);
         xc.all();
-        amx = fmaxf(amx, xc.am);
+        amx = h2_nanmax(amx, xc.am);
     }
     __syncthreads();
     for (unsigned tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -485,7 +485,7 @@ __global__ __launch_bounds__(THREADS, 1) void dqn_chain_h2_kernel(
                 h2_dw_host<3, 12>(aW3[0], zf[1], af[0][1], e);
                 h2_dw_host<6, 12>(aW3[1], zf[0], af[1][0], e);
                 h2_dw_host<9, 12>(aW3[1], zf[1], af[1][1], e);
-                amz2 = fmaxf(amz2, e.am);
+                amz2 = h2_nanmax(amz2, e.am);
                 reinterpret_cast<unsigned*>(images + tile * (2L * DH_IMAGE_HALVES) + DH_IMAGE_HALVES)[2 * BM + (2 * wave) * 64 + lane] = e.negmask;
             }
             // db3 (wave 0) and db2 of this wave's first column tile: column sums through an all-ones operand (small term first)
@@ -511,7 +511,7 @@ __global__ __launch_bounds__(THREADS, 1) void dqn_chain_h2_kernel(
             {
                 DhDlreluOps<FS_P1> e(hi, lo, 64 * wave + 32, L.H2, lane, q2);
                 h2_gemm_host<DQN_H, FS_P1, true, true, 2, 24, 1>(wt2a, QTH + DH_OFF_QTH2, ct0, L.H2, 0, hi0, lo0, lane, e);
-                amz2 = fmaxf(amz2, e.am);
+                amz2 = h2_nanmax(amz2, e.am);
                 reinterpret_cast<unsigned*>(images + tile * (2L * DH_IMAGE_HALVES) + DH_IMAGE_HALVES)[2 * BM + (2 * wave + 1) * 64 + lane] = e.negmask;
             }
 #pragma unroll
@@ -533,7 +533,7 @@ __global__ __launch_bounds__(THREADS, 1) void dqn_chain_h2_kernel(
                 DhDz1Ops e0(hi0, lo0, hw0, zw0, q1);
                 h2_gemm_host<DQN_H, FS_P1, true>(wt2b, QTH + DH_OFF_QTH2, ct1, L.H2, 0, hi, lo, lane, e0);
                 bs1[0] += e0.colsum();
-                amz1 = fmaxf(amz1, e0.am);
+                amz1 = h2_nanmax(amz1, e0.am);
             }
             // the next tile's rows (requested ~15k cycles ago) have landed: nothing younger than them is in flight HERE (the weight rings
             // were consumed, H1's image left at the top of the backward pass), so this wait is free
@@ -550,7 +550,7 @@ __global__ __launch_bounds__(THREADS, 1) void dqn_chain_h2_kernel(
                 h2_trns<FS_PX>(xf[0], L.Xo, trx, 2, 0); h2_trns<FS_PX>(xf[1], L.Xo, trx, 2, 1);
                 h2_dw_host<12, 18>(aW1[0][2], z0, xf[0], e1); h2_dw_host<15, 18>(aW1[0][2], z1, xf[1], e1);
                 bs1[1] += e1.colsum();
-                amz1 = fmaxf(amz1, e1.am);
+                amz1 = h2_nanmax(amz1, e1.am);
             }
             {   // the second column tile's dW1 (18 MFMAs) with the NEXT tile's target-pass planes (L.xs -> L.Xt: free since this tile's
                 // target layer 1) in its gaps; its first weights requested in front
@@ -566,7 +566,7 @@ __global__ __launch_bounds__(THREADS, 1) void dqn_chain_h2_kernel(
                     h2_dw_host<6, 18>(aW1[1][1], z0, xf[0], xc); h2_dw_host<9, 18>(aW1[1][1], z1, xf[1], xc);
                     h2_trns<FS_PX>(xf[0], L.Xo, trx, 2, 0); h2_trns<FS_PX>(xf[1], L.Xo, trx, 2, 1);
                     h2_dw_host<12, 18>(aW1[1][2], z0, xf[0], xc); h2_dw_host<15, 18>(aW1[1][2], z1, xf[1], xc);
-                    amx = fmaxf(amx, xc.am);
+                    amx = h2_nanmax(amx, xc.am);
                 } else {
 #pragma unroll
                     for (int kt = 0; kt < 3; ++kt) {
@@ -621,9 +621,9 @@ __global__ __launch_bounds__(THREADS, 1) void dqn_chain_h2_kernel(
     __syncthreads();
     for (int c = wave; c < DH_NMAX; c += NWAVE) {
         const float* a = L.amax + c * THREADS;
-        float m = fmaxf(fmaxf(a[lane], a[lane + 64]), fmaxf(a[lane + 128], a[lane + 192]));
+        float m = h2_nanmax(h2_nanmax(a[lane], a[lane + 64]), h2_nanmax(a[lane + 128], a[lane + 192]));     // (a NaN survives)
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        for (int o = 32; o > 0; o >>= 1) m = h2_nanmax(m, __shfl_xor(m, o, 64));
         if (lane == 0) wsmax[(long)blockIdx.x * H2_NACT_CLASSES + c] = m;
     }
 }

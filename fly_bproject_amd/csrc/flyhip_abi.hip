@@ -64,7 +64,7 @@ extern "C" hipError_t flyhip_launch_mlp_adam(float* P, float* PF, float* PT, con
                                              float max_norm, float grad_scale, float* norm_ws, int norm_ready,
                                              uint16_t* PB, uint16_t* PTB, const int* idx_fb, const int* idx_tb,
                                              int* step_out, const int* grad_invalid, uint16_t* PH, uint16_t* PTH,
-                                             float* h2_scales, int h2_rescale, void* stream);
+                                             float* h2_scales, int h2_period, void* stream);
 extern "C" hipError_t flyhip_launch_mlp_h2_rescale(const float* P, const int* idx_fb, const int* idx_tb, uint16_t* PH, uint16_t* PTH,
                                                    float* h2_scales, void* stream);
 extern "C" int64_t flyhip_mlp_fused_h2_workspace_floats(void);
@@ -175,7 +175,7 @@ int launch(FlyHandle h, int phases, const float* actions, const FlyBuffers* b, v
 extern "C" {
 
 const char* fly_last_error(void) { return g_err; }
-int fly_abi_version(void) { return 12; }
+int fly_abi_version(void) { return 13; }
 
 int fly_create(const FlyConfig* cfg, FlyHandle* out)
 {
@@ -506,7 +506,7 @@ int mlp_adam_step(float* params, float* params_frag, float* params_t_frag, const
                   float* exp_avg_sq, int32_t* step, float lr, float beta1, float beta2, float eps,
                   float max_norm, float grad_scale, float* norm_ws, int32_t norm_ready, uint16_t* params_b3,
                   uint16_t* params_t_b3, const int32_t* idx_b3, const int32_t* idx_t_b3, int32_t* step_out,
-                  const int32_t* grad_invalid, uint16_t* params_h2, uint16_t* params_t_h2, float* h2_scales, int32_t h2_rescale,
+                  const int32_t* grad_invalid, uint16_t* params_h2, uint16_t* params_t_h2, float* h2_scales, int32_t h2_period,
                   void* stream)
 {
     if (params_b3 && (!params_t_b3 || !idx_b3 || !idx_t_b3))
@@ -518,7 +518,7 @@ int mlp_adam_step(float* params, float* params_frag, float* params_t_frag, const
         return fail(FLY_E_ARG, "mlp_adam_step: null pointer");
     hipError_t e = flyhip_launch_mlp_adam(params, params_frag, params_t_frag, idx_frag, idx_t_frag, grad, mask, exp_avg, exp_avg_sq, step, lr, beta1, beta2,
                                           eps, max_norm, grad_scale, norm_ws, norm_ready, params_b3, params_t_b3, idx_b3, idx_t_b3,
-                                          step_out, grad_invalid, params_h2, params_t_h2, h2_scales, h2_rescale, stream);
+                                          step_out, grad_invalid, params_h2, params_t_h2, h2_scales, h2_period, stream);
     if (e != hipSuccess) return hip_fail(e, "mlp_adam_step launch");
     return FLY_OK;
 }

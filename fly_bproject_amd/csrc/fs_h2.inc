@@ -27,6 +27,16 @@ constexpr int H2C_X = 0, H2C_H1 = 1, H2C_H2 = 2, H2C_H3 = 3, H2C_Z4 = 4, H2C_Z3 
 constexpr int H2_TARGET_EXP_ACT = 7, H2_TARGET_EXP_GRAD = 2;
 __host__ __device__ constexpr int h2_target_exp(int c) { return c < 4 ? H2_TARGET_EXP_ACT : H2_TARGET_EXP_GRAD; }
 constexpr float H2_F16_MAX = 65504.0f;
+// Scales lagging HIGH: a class maximum that falls k binades between two launches meets scales 2^k too large, and its elements lose k
+// bits above the second term's fixed absolute quantum (fp16's subnormal step, 2^-24).  Measured on the PPO step with the gradient
+// classes' scales 2^k too large (tests/test_h2_edges_gpu.py, profiles/h2_lagging_scales.txt), worst chain / dW / db error relative to
+// its fp64 scale: k = 4: 2.3e-6, k = 6: 5.5e-6, k = 8: 2.0e-5, k = 11: 1.6e-4 (activations 8 binades low: 3.5e-7).  Real updates do
+// land there: in 1875 launches of the benchmark's run, 20 had a gradient class maximum below 2^-4 of |scaled value|, 1 below 2^-6,
+// none below 2^-7.  A refusal redoes the rest of the update in bf16x3 (a floor at 2^-4 refused 7 of 25 updates: 36 % slower), so
+// the floor sits below what training produces: mlp_grad_reduce_h2_kernel refuses a launch (the overflow path) only when a class
+// maximum of |scaled value| is nonzero and below H2_CLASS_FLOOR = 2^-8 -- more than 10 binades under the gradient window (accepted
+// error up to ~1e-4), more than 15 under the activation window.
+constexpr float H2_CLASS_FLOOR = 0x1p-8f;
 
 // ---- the three products ------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void h2_mfma_v(f32x16& acc, const f16x8& a, const f16x8& b)
@@ -122,11 +132,20 @@ __device__ __forceinline__ unsigned h2_cvt2(float x, float y)
     const f32x2 v = {x, y};
     return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2));
 }
-// max(m, |a|, |b|) as ONE instruction (fmaxf chains compile to canonicalising v_max_f32 pairs); a NaN operand is ignored
+// max(m, |a|, |b|) as ONE instruction (fmaxf chains compile to canonicalising v_max_f32 pairs).  v_maximum3_f32 (IEEE 754-2019
+// maximum), not v_max3_f32: a NaN operand makes the result NaN instead of being dropped, so a NaN anywhere in a class reaches the
+// class maximum, and from there the reduction's NaN test (which refuses the step).  The maxima are folded on with h2_nanmax for the
+// same reason: fmaxf (maxNum) would drop the NaN again.
 __device__ __forceinline__ float h2_max3(float m, float a, float b)
 {
     float r;
-    asm("v_max3_f32 %0, %1, |%2|, |%3|" : "=v"(r) : "v"(m), "v"(a), "v"(b));
+    asm("v_maximum3_f32 %0, %1, |%2|, |%3|" : "=v"(r) : "v"(m), "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ float h2_nanmax(float a, float b)
+{
+    float r;
+    asm("v_maximum3_f32 %0, %1, %2, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
 // (x, y) ALREADY scaled -> the pair's two packed terms
@@ -223,7 +242,7 @@ __device__ __forceinline__ void h2_colsum_step(f32x16& t, const f16x8 (&z)[2])
 __device__ __forceinline__ void h2_amax_fold(float* amax, int c, int tl, float am)
 {
     float* p = amax + c * THREADS + tl;
-    *p = fmaxf(*p, am);
+    *p = h2_nanmax(*p, am);
 }
 
 

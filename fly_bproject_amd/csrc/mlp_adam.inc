@@ -12,6 +12,35 @@ constexpr int ADAM_THREADS = 1024;
 constexpr int ADAM_WAVES = ADAM_THREADS / 64;
 constexpr int ADAM_BLOCKS = (MLP_PACKED_FLOATS + ADAM_THREADS - 1) / ADAM_THREADS;   // 73
 
+// fp16x2 weight-scale bookkeeping in the scale table `fsc` (include/flyhip.h, h2_scales), beside the class scales:
+//   [H2_SINCE + par]   applied steps whose planes were split under the current weight scales (a float);
+//   [H2_WMAX + par * H2_WMAX_SLOTS + w]   max |w| over the 64 packed elements 64 w .. 64 w + 63 as an applied step left them
+//                      (0 for a group of biases: every region boundary is a multiple of 64, so a group is all weights or all biases).
+// par = the parity of the applied-step count: the step that takes the count to s writes slot s & 1 and reads slot (s - 1) & 1, which
+// the applied step before it wrote -- no word is both read and written by one launch, and a refused step writes nothing.
+constexpr int H2_SINCE = 40;
+constexpr int H2_WMAX = 64;
+constexpr int H2_WMAX_SLOTS = (MLP_PACKED_FLOATS + 63) / 64;                        // 1161
+constexpr int H2_TABLE_FLOATS = H2_WMAX + 2 * H2_WMAX_SLOTS;                        // 2386 = MLP_H2_SCALE_FLOATS_ABI
+__device__ __forceinline__ int h2_group_layer(int w)      // weight layer of packed group w, -1: biases
+{
+    const int o = 64 * w;
+    return o < MLP_OFF_B1 ? 0 : o < MLP_OFF_W2 ? -1 : o < MLP_OFF_B2 ? 1 : o < MLP_OFF_W3 ? -1 : o < MLP_OFF_B3 ? 2 : o < MLP_OFF_W4 ? -1
+         : o < MLP_OFF_B4 ? 3 : -1;
+}
+__device__ __forceinline__ float h2_wave_max(float x)     // max over the wave's 64 lanes of x >= 0 (order-free, exact), wave-uniform
+{
+    x = fmaxf(x, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true)));
+    x = fmaxf(x, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x4E, 0xF, 0xF, true)));
+    x = fmaxf(x, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x141, 0xF, 0xF, true)));
+    x = fmaxf(x, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x140, 0xF, 0xF, true)));
+    const int b = __builtin_bit_cast(int, x);           // (each row of 16 lanes holds its maximum)
+    return fmaxf(fmaxf(__builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0)), __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16))),
+                 fmaxf(__builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32)), __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48))));
+}
+static_assert(MLP_OFF_B1 % 64 == 0 && MLP_OFF_W2 % 64 == 0 && MLP_OFF_B2 % 64 == 0 && MLP_OFF_W3 % 64 == 0 && MLP_OFF_B3 % 64 == 0 &&
+              MLP_OFF_W4 % 64 == 0 && MLP_OFF_B4 % 64 == 0, "a 64-element group (one wave of the apply kernel) lies in one region");
+
 __global__ __launch_bounds__(ADAM_THREADS) void mlp_adam_norm_kernel(const float* __restrict__ G,
                                                                      const float* __restrict__ mask, float grad_scale,
                                                                      float* __restrict__ norm_ws, int* __restrict__ step,
@@ -52,7 +81,7 @@ __global__ __launch_bounds__(ADAM_THREADS) void mlp_adam_apply_kernel(float* __r
                                                                       int* __restrict__ step_out,
                                                                       const int* __restrict__ grad_invalid,
                                                                       u16* __restrict__ PH, u16* __restrict__ PTH,
-                                                                      float* __restrict__ fsc, int h2_rescale)
+                                                                      float* __restrict__ fsc, int h2_period)
 {
     __shared__ float s_coef, s_step_size, s_bc2_sqrt;
     __shared__ float red[ADAM_WAVES];
@@ -77,6 +106,7 @@ __global__ __launch_bounds__(ADAM_THREADS) void mlp_adam_apply_kernel(float* __r
     const float mk = live ? mask[i] : 0.0f, g_in = live ? G[i] : 0.0f, m_in = live ? m[i] : 0.0f, v_in = live ? v[i] : 0.0f,
                 p_in = live ? P[i] : 0.0f;
     const int jf = live ? idx_f[i] : -1, jt = live ? idx_t[i] : -1;
+    const int step_now = self_norm ? *step + 1 : *step;     // applied steps once this one is (norm_ready: already advanced)
     {   // every block re-adds the same partial sums in the same order: identical clip coefficient
         float t = 0.0f;
         if (self_norm) {
@@ -92,23 +122,31 @@ __global__ __launch_bounds__(ADAM_THREADS) void mlp_adam_apply_kernel(float* __r
         for (int o = 32; o > 0; o >>= 1) t += __shfl_down(t, o, 64);
         if ((tid & 63) == 0) red[tid >> 6] = t;
     }
-    // fp16x2 weight planes: layer l's weights are split as w s_l = h0 + h1 under a scale that stays fixed between two RESCALE steps
-    // (h2_rescale != 0: every <= 64 steps).  A rescale step derives s_l from the weights as they stand BEFORE this step -- every block
-    // takes the same maxima over the whole of P (297 KB from L2) --: max(max |w_l|, 2^-4) -> [2^11, 2^12), 16x below fp16's largest
-    // value.  An Adam step moves a weight by at most lr (1 - beta1) / sqrt(1 - beta2) = 3.2 lr, so over the <= 65 steps a scale serves
-    // a weight travels < 0.21, while overflowing needs it to grow to 16 max(max |w_l|, 2^-4) >= 1: it cannot.
-    if (PH && !h2_rescale && tid < 4) s_wscale[tid] = fsc[8 + tid];
-    if (PH && h2_rescale) {
+    // fp16x2 weight planes: layer l's weights are split as w s_l = h0 + h1 under a scale that stays fixed between two RESCALE steps.
+    // The count of applied steps since the scales were derived lives in the table (H2_SINCE), so a refused step neither counts nor
+    // uses up a rescale: the first APPLIED step that finds the count at h2_period (the host: min(64, 0.9 / (3.2 lr))) rescales.  A
+    // rescale step derives s_l from the weights as they stand BEFORE this step: the per-group maxima the previous applied step
+    // published (H2_WMAX, the slot of the other parity: no block of this launch writes it; mlp_h2_rescale seeds both), the same in
+    // every block -- max(max |w_l|, 2^-4) -> [2^11, 2^12), 16x below fp16's largest value.  An Adam step moves a weight by at most
+    // lr (1 - beta1) / sqrt(1 - beta2) = 3.2 lr, so over the <= h2_period + 1 steps a scale serves a weight travels < 0.21, while
+    // overflowing needs it to grow to 16 max(max |w_l|, 2^-4) >= 1: it cannot.
+    const int par = step_now & 1;
+    bool rescale = false;
+    if (PH) {
+        const float s0 = fsc[H2_SINCE], s1 = fsc[H2_SINCE + 1];     // (both words: the loads need not wait for *step)
+        const int since = (int)(par ? s0 : s1);
+        rescale = since >= h2_period;
+        if (blockIdx.x == 0 && tid == 0) fsc[H2_SINCE + par] = rescale ? 1.0f : (float)(since + 1);
+    }
+    if (PH && !rescale && tid < 4) s_wscale[tid] = fsc[8 + tid];
+    if (PH && rescale) {
         if (tid < 4) s_wmax[tid] = 0u;
         __syncthreads();
         float mx[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        const float4* p4 = reinterpret_cast<const float4*>(P);
-        for (int q = tid; q < MLP_PACKED_FLOATS / 4; q += ADAM_THREADS) {
-            const int o = 4 * q;
-            const int l = o < MLP_OFF_B1 ? 0 : o < MLP_OFF_W2 ? -1 : o < MLP_OFF_B2 ? 1 : o < MLP_OFF_W3 ? -1 : o < MLP_OFF_B3 ? 2 : o < MLP_OFF_W4 ? -1
-                        : o < MLP_OFF_B4 ? 3 : -1;
-            const float4 w = p4[q];
-            const float a = fmaxf(fmaxf(fabsf(w.x), fabsf(w.y)), fmaxf(fabsf(w.z), fabsf(w.w)));
+        const float* wm = fsc + H2_WMAX + (par ^ 1) * H2_WMAX_SLOTS;
+        for (int w = tid; w < H2_WMAX_SLOTS; w += ADAM_THREADS) {
+            const int l = h2_group_layer(w);
+            const float a = wm[w];
 #pragma unroll
             for (int k = 0; k < 4; ++k) mx[k] = l == k ? fmaxf(mx[k], a) : mx[k];
         }
@@ -137,7 +175,6 @@ __global__ __launch_bounds__(ADAM_THREADS) void mlp_adam_apply_kernel(float* __r
         s_coef = coef < 1.0f ? coef : 1.0f;
         if (blockIdx.x == 0) norm_ws[0] = norm;
         // bias corrections of torch.optim.Adam, once per workgroup (two powf per thread otherwise)
-        const int step_now = self_norm ? *step + 1 : *step;
         if (self_norm && blockIdx.x == 0) *step_out = step_now;
         const float ts = (float)step_now;
         const float bc1 = 1.0f - powf(beta1, ts);
@@ -146,38 +183,46 @@ __global__ __launch_bounds__(ADAM_THREADS) void mlp_adam_apply_kernel(float* __r
         s_bc2_sqrt = sqrtf(bc2);
     }
     __syncthreads();
-    if (!live) return;
-    const float coef = s_coef * grad_scale;
-    const float step_size = s_step_size;
-    const float bc2_sqrt = s_bc2_sqrt;
-    const float g = g_in * coef * mk;
-    const float mi = beta1 * m_in + (1.0f - beta1) * g;
-    const float vi = beta2 * v_in + (1.0f - beta2) * g * g;
-    m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    const float p = p_in - mk * (step_size * (mi / denom));
-    P[i] = p;
-    // keep the fragment-ordered copies the kernels stream in step with the master weights
-    if (jf >= 0) PF[jf] = p;
-    if (jt >= 0) PT[jt] = p;
-    int kf = -1, kt = -1;
-    if (PB) {       // and the three-term bf16 planes of the bf16x3 GEMM path
-        u16 a, b, c;
-        split3(p, a, b, c);
-        kf = idx_fb[i]; kt = idx_tb[i];
-        if (kf >= 0) { PB[kf] = a; PB[kf + 512] = b; PB[kf + 1024] = c; }
-        if (kt >= 0) { PTB[kt] = a; PTB[kt + 512] = b; PTB[kt + 1024] = c; }
+    float p = 0.0f;
+    if (live) {
+        const float coef = s_coef * grad_scale;
+        const float step_size = s_step_size;
+        const float bc2_sqrt = s_bc2_sqrt;
+        const float g = g_in * coef * mk;
+        const float mi = beta1 * m_in + (1.0f - beta1) * g;
+        const float vi = beta2 * v_in + (1.0f - beta2) * g * g;
+        m[i] = mi; v[i] = vi;
+        const float denom = sqrtf(vi) / bc2_sqrt + eps;
+        p = p_in - mk * (step_size * (mi / denom));
+        P[i] = p;
+        // keep the fragment-ordered copies the kernels stream in step with the master weights
+        if (jf >= 0) PF[jf] = p;
+        if (jt >= 0) PT[jt] = p;
+        int kf = -1, kt = -1;
+        if (PB) {       // and the three-term bf16 planes of the bf16x3 GEMM path
+            u16 a, b, c;
+            split3(p, a, b, c);
+            kf = idx_fb[i]; kt = idx_tb[i];
+            if (kf >= 0) { PB[kf] = a; PB[kf + 512] = b; PB[kf + 1024] = c; }
+            if (kt >= 0) { PTB[kt] = a; PTB[kt + 512] = b; PTB[kt + 1024] = c; }
+        }
+        if (PH && kf >= 0) {    // and the two-term fp16 planes of the fp16x2 step (PB's layout with 1024-word blocks instead of 1536), under
+            // the layer's scale
+            const int layer = i < MLP_OFF_W2 ? 0 : i < MLP_OFF_W3 ? 1 : i < MLP_OFF_W4 ? 2 : 3;
+            const float ps = p * s_wscale[layer];
+            const _Float16 h0 = (_Float16)ps;
+            const _Float16 h1 = (_Float16)(ps - (float)h0);
+            const u16 a = __builtin_bit_cast(u16, h0), b = __builtin_bit_cast(u16, h1);
+            const int hf = (kf / 1536) * 1024 + kf % 1536;
+            PH[hf] = a; PH[hf + 512] = b;
+            if (kt >= 0) { const int ht = (kt / 1536) * 1024 + kt % 1536; PTH[ht] = a; PTH[ht + 512] = b; }
+        }
     }
-    if (PH && kf >= 0) {    // and the two-term fp16 planes of the fp16x2 step (PB's layout with 1024-word blocks instead of 1536), under the
-        // layer's scale
-        const int layer = i < MLP_OFF_W2 ? 0 : i < MLP_OFF_W3 ? 1 : i < MLP_OFF_W4 ? 2 : 3;
-        const float ps = p * s_wscale[layer];
-        const _Float16 h0 = (_Float16)ps;
-        const _Float16 h1 = (_Float16)(ps - (float)h0);
-        const u16 a = __builtin_bit_cast(u16, h0), b = __builtin_bit_cast(u16, h1);
-        const int hf = (kf / 1536) * 1024 + kf % 1536;
-        PH[hf] = a; PH[hf + 512] = b;
-        if (kt >= 0) { const int ht = (kt / 1536) * 1024 + kt % 1536; PTH[ht] = a; PTH[ht + 512] = b; }
+    if (PH) {   // publish this wave's max |w| of the weights it leaves, for the next rescale step (a wave is one group of 64)
+        const int w = i >> 6;
+        float mw = 0.0f;
+        if (h2_group_layer(w) >= 0) mw = h2_wave_max(fabsf(p));        // (wave-uniform branch)
+        if ((tid & 63) == 0 && w < H2_WMAX_SLOTS) fsc[H2_WMAX + par * H2_WMAX_SLOTS + w] = mw;
     }
 }
 
@@ -218,6 +263,16 @@ __global__ __launch_bounds__(H2_RESCALE_THREADS) void mlp_h2_rescale_kernel(cons
         fsc[16 + 8 + tid] = 1.0f / sc;
     }
     __syncthreads();
+    // seed what the next mlp_adam_apply_kernel reads, whichever parity it takes: no applied step since the scales were derived, and
+    // the per-group maxima of the weights as they stand
+    if (tid < 2) fsc[H2_SINCE + tid] = 0.0f;
+    for (int w = tid; w < H2_WMAX_SLOTS; w += H2_RESCALE_THREADS) {
+        float m = 0.0f;
+        if (h2_group_layer(w) >= 0)
+            for (int j = 64 * w; j < 64 * w + 64; ++j) m = fmaxf(m, fabsf(P[j]));
+        fsc[H2_WMAX + w] = m;
+        fsc[H2_WMAX + H2_WMAX_SLOTS + w] = m;
+    }
     for (int i = tid; i < MLP_PACKED_FLOATS; i += H2_RESCALE_THREADS) {
         const int kf = idx_fb[i];
         if (kf < 0) continue;

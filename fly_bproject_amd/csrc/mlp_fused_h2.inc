@@ -11,7 +11,7 @@
 // `fsc` (device, H2_FSC_FLOATS floats) holds s[c] at [c] and 1 / s[c] at [16 + c].  A dW accumulator lives across all of a workgroup's
 // tiles and contracts over rows, so a class has ONE scale per launch.  Products of powers of two are exact: every epilogue applies
 // 1 / (s_a s_w) to hi + lo, i.e. computes on the very fp32 values an unscaled kernel would see.
-// Where the scales come from: every value that is split also folds |scaled value| into a running maximum (one v_max3_f32 per pair);
+// Where the scales come from: every value that is split also folds |scaled value| into a running maximum (one v_maximum3_f32 per pair: a NaN survives into it);
 // each workgroup leaves its eight class maxima behind its slab, the slab reduction (mlp_grad_reduce_h2_kernel) takes the maximum over
 // workgroups and sets the NEXT launch's scales so that this launch's maximum would land in the class's window (h2_target_exp below:
 // 2^8 of headroom under 65504 for activations, 2^13 for gradients).  A maximum of 65504 or more means some value of THIS launch did not fit: the reduction marks
@@ -421,7 +421,7 @@ __global__ __launch_bounds__(THREADS, 1) void mlp_fused_step_h2_kernel(
                 {
                     H2EluOps<FS_P1, DUMP> e(hi, lo, bias1, 64 * wave + 32, H1, lane, d_h1, nvalid, k1, s1, is1);
                     h2_gemm_host<MLP_H1, FS_P1, false, true, 2, 24, 1, 2 * MLP_H2 * (MLP_H1 / 2)>(w2a, PH + H2_OFF_PH2, wave, H1, 0, hi0, lo0, lane, e);
-                    am = fmaxf(am, e.am);
+                    am = h2_nanmax(am, e.am);
                 }
                 h2_amax_fold(amax, H2C_H1, tl, am);
                 hi = hi0; lo = lo0;
@@ -686,7 +686,7 @@ __global__ __launch_bounds__(THREADS, 1) void mlp_fused_step_h2_kernel(
 #undef H2_P8_STEP
                     if (STAMP && t == 0) stamp<STAMP>(stamps, 17);
                     bs1[t] += ez.zsum;
-                    am1 = fmaxf(am1, ez.am);
+                    am1 = h2_nanmax(am1, ez.am);
 #pragma unroll
                     for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -793,9 +793,9 @@ __global__ __launch_bounds__(THREADS, 1) void mlp_fused_step_h2_kernel(
     for (int j = 0; j < 2; ++j) {
         const int c = 2 * wave + j;
         const float* a = amax + c * THREADS;
-        float m = fmaxf(fmaxf(a[lane], a[lane + 64]), fmaxf(a[lane + 128], a[lane + 192]));
+        float m = h2_nanmax(h2_nanmax(a[lane], a[lane + 64]), h2_nanmax(a[lane + 128], a[lane + 192]));     // (a NaN survives)
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        for (int o = 32; o > 0; o >>= 1) m = h2_nanmax(m, __shfl_xor(m, o, 64));
         if (lane == 0) wsmax[(long)wg * H2_NACT_CLASSES + c] = m;
     }
     if (STAMP) {
@@ -807,7 +807,8 @@ __global__ __launch_bounds__(THREADS, 1) void mlp_fused_step_h2_kernel(
 
 // ---- the slab reduction of the fp16x2 step: mlp_grad_reduce_kernel's sum (chunked slabs, fixed order) + the scale bookkeeping ----------
 // Block 0 also: takes the class maxima over the workgroups, writes the NEXT launch's scales into `fsc`, and decides whether THIS launch's
-// values fit fp16.  If not (or while the sticky word *ovf is set: a previous step of this update did not fit, and the optimizer must
+// values fit fp16: no class maximum >= 65504, none NaN (a NaN anywhere in a class reaches its maximum: h2_max3 / h2_nanmax), none
+// below H2_CLASS_FLOOR (scales lagging too far above the data).  If not (or while the sticky word *ovf is set: a previous step of this update did not fit, and the optimizer must
 // refuse every step from there on so that the host can redo them IN ORDER) the gradient is marked invalid (G[MLP_ERR_SLOT] = 1) and
 // the step counter is not advanced.
 constexpr int H2_ERR_SLOT = MLP_OFF_W1 + 76;
@@ -838,7 +839,7 @@ __global__ __launch_bounds__(64 * H2_RED_WAVES) void mlp_grad_reduce_h2_kernel(c
         nan = __any(nan);
         if (lane == 0) {
             const float s_old = fsc[c];
-            const bool over = nan || !(m < H2_F16_MAX);
+            const bool over = nan || !(m < H2_F16_MAX) || (m > 0.0f && m < H2_CLASS_FLOOR);   // (the floor: fs_h2.inc)
             float s_new = s_old;
             if (nan || !(m < 3.0e38f)) s_new = s_old * 0.00390625f;                     // nothing to go by: back off by 2^-8
             else if (m > 0.0f) s_new = ldexpf(s_old, h2_target_exp(c) - ilogbf(m));     // this launch's maximum -> its class's window

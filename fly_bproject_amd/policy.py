@@ -102,7 +102,8 @@ def build_plane_maps():
 
 # fp16x2 planes of the fused optimizer step (csrc/mlp_fused_h2.inc): PB's / PTB's layout with two terms per k block
 PH_HALVES, PTH_HALVES = PB_HALVES * 2 // 3, PTB_HALVES * 2 // 3
-H2_SCALE_FLOATS, H2_INV, H2_W0 = 48, 16, 8
+H2_SCALE_FLOATS, H2_INV, H2_W0 = 2386, 16, 8        # (csrc/mlp_adam.inc: [40, 41] and [64 ..) are mlp_adam_step's rescale bookkeeping)
+H2_SINCE, H2_WMAX, H2_WMAX_SLOTS = 40, 64, 1161
 H2_CLASSES = ("x", "h1", "h2", "h3", "dz4", "dz3", "dz2", "dz1")
 
 
@@ -170,7 +171,6 @@ class PackedPolicy:
         self.h2_overflow = torch.zeros(1, dtype=torch.int32, device=self.device)     # sticky: a launch's values did not fit fp16
         self.h2_freeze = False              # tests: the reduction leaves the scale table alone
         self.h2_calibrated = False
-        self._h2_steps_since_rescale = 0
         self.h2_suspended = False           # True while refused steps are redone on the bf16x3 kernel (the planes stay maintained)
         self.h2_overflows = 0               # updates in which the fp16x2 step was refused and redone on bf16x3
         self._h2_reset_scales()
@@ -222,11 +222,13 @@ class PackedPolicy:
 
     def refresh(self):
         """Rebuild the fragment-ordered copies from the master weights (after a load or any
-        out-of-band change of the parameters; mlp_adam_step keeps them in step by itself)."""
+        out-of-band change of the parameters; mlp_adam_step keeps them in step by itself).  The fp16x2
+        activation / gradient scales were measured on the old weights: the next update calibrates again."""
         with torch.no_grad():
             self.PF[self._dst_f] = self.P[self._src_f]
             self.PT[self._dst_t] = self.P[self._src_t]
             self._refresh_planes()
+        self.h2_calibrated = False
         self.version += 1
 
     refresh_transposes = refresh
@@ -256,13 +258,13 @@ class PackedPolicy:
     def _refresh_planes_h2(self):
         """fp16x2 weight planes and their per-layer scales from the master weights (`mlp_h2_rescale`: one small launch, no host sync).
         The scales then stay fixed while mlp_adam_step splits the updated weights under them; an Adam step moves a weight by at most
-        3.2 lr, and overflowing needs a weight to travel 15/16 at least, so a call every `0.9 / (3.2 lr)` steps keeps fp16 safe."""
+        3.2 lr, and overflowing needs a weight to travel 15/16 at least, so a rescale every `0.9 / (3.2 lr)` applied steps keeps fp16
+        safe (mlp_adam_step rescales by itself; this launch also seeds its bookkeeping in the table)."""
         if self.device.type != "cuda":
             return                                  # (layout-only uses of the class on the CPU: tests/test_dist_cpu.py)
         p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
         _lib.check(self._lib.mlp_h2_rescale(p(self.P), p(self.idx_fb), p(self.idx_tb), p(self.PH), p(self.PTH), p(self.h2_scales),
                                             _lib.stream_ptr()), "mlp_h2_rescale")
-        self._h2_steps_since_rescale = 0
 
     def _planes_live(self):
         return self._gemm == "bf16x3" or self.gemm_infer == "bf16x3"
@@ -313,11 +315,11 @@ class PackedPolicy:
         if not self.h2_live():
             return (None, None, None, C.c_int(0))
         p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
-        # a RESCALE step (the kernel re-derives the weight scales from the weights before it splits under them) often enough that a
-        # weight cannot have drifted out of the scale's 16x headroom: an Adam step moves it by at most 3.2 lr
-        rescale = self._h2_steps_since_rescale >= max(1, min(64, int(0.9 / (3.2 * self.lr))))
-        self._h2_steps_since_rescale = 1 if rescale else self._h2_steps_since_rescale + 1
-        return (p(self.PH), p(self.PTH), p(self.h2_scales), C.c_int(1 if rescale else 0))
+        # a RESCALE step (the kernel re-derives the weight scales from the weights before it splits under them) every `period` APPLIED
+        # steps -- the kernel counts them on the device, a refused step does not count --, often enough that a weight cannot have
+        # drifted out of the scale's 16x headroom: an Adam step moves it by at most 3.2 lr
+        period = max(1, min(64, int(0.9 / (3.2 * self.lr))))
+        return (p(self.PH), p(self.PTH), p(self.h2_scales), C.c_int(period))
 
     def pb_ptr(self):
         """Term planes for the UPDATE's forward (minibatch_grad); inference launches (rollout policy,

@@ -372,7 +372,7 @@ int mlp_adam_step(float* params, float* params_frag, float* params_t_frag, const
                   float max_norm, float grad_scale, float* norm_ws, int32_t norm_ready,
                   uint16_t* params_b3, uint16_t* params_t_b3, const int32_t* idx_b3,
                   const int32_t* idx_t_b3, int32_t* step_out, const int32_t* grad_invalid,
-                  uint16_t* params_h2, uint16_t* params_t_h2, float* h2_scales, int32_t h2_rescale, void* stream);
+                  uint16_t* params_h2, uint16_t* params_t_h2, float* h2_scales, int32_t h2_period, void* stream);
 
 /*
  * The same gradient in the fp16x2 arithmetic (csrc/mlp_fused_h2.inc): every fp32 operand of a GEMM is carried as TWO fp16 terms of
@@ -381,14 +381,17 @@ int mlp_adam_step(float* params, float* params_frag, float* params_t_frag, const
  *   params_h2 / params_t_h2  the weights as two fp16 terms of w * s_layer (MLP_PH_HALVES_ABI / MLP_PTH_HALVES_ABI 16-bit words: the
  *                 layout of params_b3 / params_t_b3 with 1024-word blocks instead of 1536: term 0, term 1); mlp_adam_step
  *                 splits every updated weight into them (params_h2 != NULL; it needs params_b3 and its index maps too) under the
- *                 layer scales h2_scales[8 .. 11]; a call with h2_rescale != 0 first re-derives those scales from the weights as they
- *                 stand (max(max |w_layer|, 2^-4) -> [2^11, 2^12): 16x of headroom) and publishes them.  An Adam step moves a weight by
- *                 <= 3.2 lr, so a rescale step at least every 0.9 / (3.2 lr) steps (the host: every 64) keeps the planes inside fp16;
+ *                 layer scales h2_scales[8 .. 11].  The applied step that finds h2_period (>= 1) applied steps since those scales
+ *                 were derived first re-derives them from the weights as they stood before it (max(max |w_layer|, 2^-4) ->
+ *                 [2^11, 2^12): 16x of headroom) and publishes them; a refused step neither counts nor rescales.  An Adam step moves
+ *                 a weight by <= 3.2 lr, so h2_period <= 0.9 / (3.2 lr) (the host: min(64, that)) keeps the planes inside fp16;
  *   h2_scales     device float [MLP_H2_SCALE_FLOATS_ABI]: s[c] at [c], 1 / s[c] at [16 + c] for the classes c = 0 X, 1 H1, 2 H2,
- *                 3 H3, 4 dZ4, 5 dZ3, 6 dZ2, 7 dZ1, 8 .. 11 W1 .. W4; [32 + c] = the largest |scaled value| the last launch saw.
+ *                 3 H3, 4 dZ4, 5 dZ3, 6 dZ2, 7 dZ1, 8 .. 11 W1 .. W4; [32 + c] = the largest |scaled value| the last launch saw;
+ *                 [40, 41] and [64 ..) = mlp_adam_step's rescale bookkeeping (applied steps since the weight scales were derived,
+ *                 per-64-element maxima of |w| the last applied step left: csrc/mlp_adam.inc), which mlp_h2_rescale seeds.
  *                 The launch READS the table and its reduction WRITES the activation / gradient entries for the NEXT launch (this
  *                 launch's class maxima steered into [2^9, 2^10)) unless `freeze` != 0;
- *   h2_overflow   device int32, STICKY: set when a value of some launch did not fit fp16 (class maximum >= 65504).  From then on
+ *   h2_overflow   device int32, STICKY: set when a value of some launch did not fit fp16 (class maximum >= 65504) or was NaN.  From then on
  *                 every launch marks its gradient invalid (grad[76] = 1, as mlp_grad_w does with a nonzero `err`) and does not
  *                 advance *norm_step, so mlp_adam_step refuses the step: the caller reads the step counter at the end of the
  *                 update, clears the word and redoes the refused steps, in order, with mlp_fused_grad;
@@ -399,7 +402,7 @@ int mlp_adam_step(float* params, float* params_frag, float* params_t_frag, const
  */
 #define MLP_PH_HALVES_ABI 147456
 #define MLP_PTH_HALVES_ABI 106496
-#define MLP_H2_SCALE_FLOATS_ABI 48
+#define MLP_H2_SCALE_FLOATS_ABI 2386
 int mlp_h2_rescale(const float* params, const int32_t* idx_b3, const int32_t* idx_t_b3, uint16_t* params_h2, uint16_t* params_t_h2,
                    float* h2_scales, void* stream);
 int64_t mlp_fused_h2_workspace_floats(void);
@@ -493,7 +496,7 @@ int dqn_fused_update(const float* params, const uint16_t* params_b3, const uint1
  * CURRENT params / target_params (params_h2 DQN_QH_HALVES_ABI, params_t_h2 DQN_QTH_HALVES_ABI, target_params_h2 DQN_QH_HALVES_ABI
  * 16-bit words: scratch the library owns the contents of; idx_b3 / idx_t_b3 = dqn_adam_soft_update's plane maps), the two persistent
  * launches, the slab reduction, and the NEXT call's activation / gradient scales from this call's class maxima.
- *   h2_scales    device float [MLP_H2_SCALE_FLOATS_ABI]: s[c] at [c], 1 / s[c] at [16 + c], the last call's maximum of |scaled value|
+ *   h2_scales    device float [48]: s[c] at [c], 1 / s[c] at [16 + c], the last call's maximum of |scaled value|
  *                at [32 + c]; classes 0 X, 1 H1, 2 H2, 5 dZ2, 6 dZ1 (lagged), 8 .. 10 / 11 .. 13 online / target W1 .. W3 (exact, per
  *                call).  Start it at 1.0 / 1.0 / 0 and run two calls with flags = 2 on the first update's chunks.
  *   h2_overflow  device int: set to 1 when a value of THIS call did not fit fp16 under the lagged scales -- `grad` is then invalid.

@@ -50,3 +50,18 @@ def test_trainer_flags_match_reference():
     assert a.num_envs == 300 and a.save and a.load and a.record and a.testing and a.sim_device == "cuda:0"
     d = trainer.parse_args([])
     assert d.num_envs == 1000 and d.save_freq == 100 and d.time_steps_per_recorded_frame == 2 and not d.save
+
+
+def test_refresh_asks_for_a_new_fp16x2_calibration():
+    """PackedPolicy.refresh() follows an out-of-band change of the weights (a loaded checkpoint, averaged ranks): the fp16x2 step's
+    activation / gradient scales were measured on the old network, so the next update must calibrate them again."""
+    from fly_bproject_amd.policy import PackedPolicy
+    from fly_bproject_amd.ppo import Net
+    torch.manual_seed(0)
+    pol = PackedPolicy(Net(73, 18), "cpu")              # layout tables only (no kernel is launched on the CPU)
+    pol.h2_calibrated = True
+    with torch.no_grad():
+        pol.P.mul_(0.5)
+    pol.refresh()
+    assert not pol.h2_calibrated
+    assert torch.equal(pol.PF[pol._dst_f], pol.P[pol._src_f])

@@ -23,9 +23,11 @@ def lib():
     return _lib
 
 
-def test_library_is_the_hip_build(lib):
+def test_library_is_the_hip_build_of_abi_13(lib):
+    """ABI 13: mlp_adam_step's last int is the rescale period (applied steps, counted on the device) and the fp16x2 scale table holds
+    the optimizer's rescale bookkeeping (MLP_H2_SCALE_FLOATS_ABI = 2386)."""
     l = lib.load()
-    assert l.fly_abi_version() == lib.ABI_VERSION == 12
+    assert l.fly_abi_version() == lib.ABI_VERSION == 13
     assert torch.cuda.is_available() and "gfx950" in torch.cuda.get_device_properties(0).gcnArchName
 
 
