@@ -19,6 +19,12 @@ class FlyBuffers(C.Structure):
                                           "done_return", "done_length", "done_count")]
 
 
+class FlyRenderConfig(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fov_y_deg", C.c_float), ("cam_offset", C.c_float * 3),
+                ("look_z", C.c_float)]
+
+
+POSE_FLOATS = 25        # FLY_POSE_FLOATS: root pos xyz | quat xyzw | 18 joint angles
 ABI_VERSION = 13        # include/flyhip.h as this package binds it (fly_abi_version(): argument lists changed between versions)
 # name -> argtypes; every entry point returns int except fly_last_error
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
@@ -32,6 +38,8 @@ SYMBOLS = {
     "fly_integrate": [_P, C.POINTER(FlyBuffers), _P],
     "fly_pack_obs": [_P, C.POINTER(FlyBuffers), _P],
     "fly_pack_reward": [_P, C.POINTER(FlyBuffers), _I, _P],
+    "fly_set_pose_record": [_P, _P],
+    "fly_render": [_P, _P, _I, C.POINTER(FlyRenderConfig), _P, _P, _P],
     "ppo_sample_logprob": [_P, _P, _P, _P, _P, _L, _P],
     "ppo_td_gae": [_P, _P, _P, _P, _F, _F, _L, _L, _P, _P, _I, _P],
     "ppo_adv_stats": [_P, _L, _P, _P],

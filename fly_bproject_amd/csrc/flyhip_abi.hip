@@ -103,7 +103,9 @@ extern "C" hipError_t flyhip_launch_rollout_all(const FlyConfig* dcfg, const Fly
                                                 float var_decay, float var_min, float* act_all, float* logp_all, float* v_ring,
                                                 float* reward_all, int T, const int* rows_applied, const uint16_t* PB,
                                                 int64_t* reset_rows, int64_t* progress_rows, void* stream,
-                                                unsigned long long* stamps);
+                                                unsigned long long* stamps, float* poses);
+extern "C" hipError_t flyhip_launch_render(const FlyConfig* dcfg, const float* poses, int frames, const FlyRenderConfig* rc,
+                                           uint32_t* rgba_out, uint8_t* id_out, void* stream);
 extern "C" hipError_t flyhip_launch_rollout_bookkeeping(const float* reward, int64_t rows, int64_t n, float* terms,
                                                         float* score_acc, float score_scale, float* action_var, int nvar,
                                                         float var_decay, float var_min, int* rows_applied, void* stream);
@@ -117,6 +119,7 @@ extern "C" hipError_t flyhip_launch_adv_apply(float* adv, int64_t n, const float
 struct FlyEnv {
     FlyConfig host;
     FlyConfig* dev;
+    float* poses;           // fly_set_pose_record (device [T][FLY_POSE_FLOATS], NULL = off)
 };
 
 namespace {
@@ -193,6 +196,7 @@ int fly_create(const FlyConfig* cfg, FlyHandle* out)
     if (!h) return fail(FLY_E_ARG, "out of host memory");
     h->host = *cfg;
     h->dev = nullptr;
+    h->poses = nullptr;
     hipError_t e = hipMalloc((void**)&h->dev, sizeof(FlyConfig));
     if (e != hipSuccess) { delete h; return hip_fail(e, "hipMalloc(FlyConfig)"); }
     e = hipMemcpy(h->dev, cfg, sizeof(FlyConfig), hipMemcpyHostToDevice);
@@ -250,7 +254,7 @@ static int rollout_all_impl(FlyHandle h, const FlyBuffers* b, const float* param
     if (rc) return rc;
     hipError_t e = flyhip_launch_rollout_all(h->dev, &bb, params, params_frag, obs_ring, h->host.num_envs, eps_all, var,
                                              var_decay, var_min, act_all, logp_all, v_ring, reward_all, T, rows_applied,
-                                             params_b3, reset_rows, progress_rows, stream, stamps);
+                                             params_b3, reset_rows, progress_rows, stream, stamps, stamps ? nullptr : h->poses);
     if (e != hipSuccess) return hip_fail(e, "ppo_rollout_all launch");
     return FLY_OK;
 }
@@ -275,6 +279,32 @@ extern "C" int flyhip_debug_rollout_all_stamped(FlyHandle h, const FlyBuffers* b
     if (!stamps) return fail(FLY_E_ARG, "stamps is null");
     return rollout_all_impl(h, b, params, params_frag, obs_ring, eps_all, var, var_decay, var_min, act_all, logp_all, v_ring,
                             reward_all, T, nullptr, params_b3, reset_rows, progress_rows, stream, stamps);
+}
+
+int fly_set_pose_record(FlyHandle h, float* poses)
+{
+    if (!h) return fail(FLY_E_ARG, "handle is null");
+    if (reinterpret_cast<uintptr_t>(poses) & 3) return fail(FLY_E_ARG, "fly_set_pose_record: poses is not 4-byte aligned");
+    h->poses = poses;
+    return FLY_OK;
+}
+
+int fly_render(FlyHandle h, const float* poses, int32_t frames, const FlyRenderConfig* rc, uint32_t* rgba_out,
+               uint8_t* id_out, void* stream)
+{
+    if (!h) return fail(FLY_E_ARG, "handle is null");
+    if (!poses || !rc || !rgba_out) return fail(FLY_E_ARG, "fly_render: null pointer");
+    if (frames < 1 || frames > 65535) return fail(FLY_E_ARG, "fly_render: frames out of range (%d)", frames);
+    if (rc->width < 1 || rc->width > 4096 || rc->height < 1 || rc->height > 4096)
+        return fail(FLY_E_ARG, "fly_render: image size out of range (%d x %d)", rc->width, rc->height);
+    if (!(rc->fov_y_deg > 0.0f && rc->fov_y_deg < 180.0f)) return fail(FLY_E_ARG, "fly_render: fov_y_deg out of range");
+    if (!(rc->cam_offset[0] != 0.0f || rc->cam_offset[1] != 0.0f))
+        return fail(FLY_E_ARG, "fly_render: the camera must not look straight along z (cam_offset x, y both 0)");
+    if ((reinterpret_cast<uintptr_t>(poses) | reinterpret_cast<uintptr_t>(rgba_out)) & 3)
+        return fail(FLY_E_ARG, "fly_render: misaligned buffer");
+    hipError_t e = flyhip_launch_render(h->dev, poses, frames, rc, rgba_out, id_out, stream);
+    if (e != hipSuccess) return hip_fail(e, "fly_render launch");
+    return FLY_OK;
 }
 
 int fly_scale_actions(FlyHandle h, const float* actions, float* targets, void* stream)

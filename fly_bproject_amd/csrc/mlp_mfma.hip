@@ -74,6 +74,24 @@ __global__ __launch_bounds__(THREADS, B3 ? 1 : 2) void rollout_step_kernel(
     fly_body<PH_ALL>(c, act, b, lds, blockIdx.x, st);
 }
 
+// Pose record (fly_set_pose_record): env 0's pose after step t -- root position, quaternion xyzw, the 18 joint angles in DoF
+// order (FLY_POSE_FLOATS) -- out of the state `nx` the env step just left, i.e. exactly what root / dof_state hold after that
+// step.  Called by workgroup 0's first tile only: its lanes 0..7 are env 0, the leg lanes store their three angles and the lane
+// that stores the root in fly_body stores position and quaternion.
+__device__ __forceinline__ void store_pose(float* __restrict__ poses, int t, const FlyRegs& nx)
+{
+    const int sub = threadIdx.x;
+    if (sub >= LANES_PER_ENV) return;
+    float* p = poses + (long)t * FLY_POSE_FLOATS;
+    if (sub < FLY_NUM_LEGS) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) p[7 + 3 * sub + i] = nx.jq[i];
+    }
+    if (sub == LANES_PER_ENV - 1) {
+        p[0] = nx.r.px; p[1] = nx.r.py; p[2] = nx.r.pz; p[3] = nx.r.qx; p[4] = nx.r.qy; p[5] = nx.r.qz; p[6] = nx.r.qw;
+    }
+}
+
 // One launch per ROLLOUT (ppo.py:204-237 for T consecutive env steps): the envs of a 32-env tile depend on no other
 // tile and the policy does not change inside a rollout, so workgroup b simply loops over the T steps of ITS tile --
 // policy forward + sampling on observation row t, env step, observation row t + 1 -- with the env state carried in
@@ -84,13 +102,14 @@ __global__ __launch_bounds__(THREADS, B3 ? 1 : 2) void rollout_step_kernel(
 // that wrote it, at addresses this CU has not read before.  Bit for bit what T launches of rollout_step_kernel leave.
 // WPS = waves per SIMD the registers are budgeted for: 1 when the launch has at most one workgroup per CU (<= 8192
 // envs: the step body plus the carried env state want ~300 registers and spill at 256), 2 beyond that.
-template <bool B3, int WPS>
+// REC: store env 0's pose of every step to poses [T][FLY_POSE_FLOATS] (store_pose); the other instantiations ignore `poses`.
+template <bool B3, int WPS, bool REC>
 __global__ __launch_bounds__(THREADS, WPS) void rollout_all_kernel(
     const FlyConfig* __restrict__ c, FlyBuffers b, const float* __restrict__ P, const void* __restrict__ PF,
     float* __restrict__ obs_ring, long n, const float* __restrict__ eps_all, const float* __restrict__ var, float var_decay,
     float var_min, float* __restrict__ act_all, float* __restrict__ logp_all, float* __restrict__ v_ring,
     float* __restrict__ reward_all, int T, const int* __restrict__ rows_applied, int64_t* __restrict__ reset_rows,
-    int64_t* __restrict__ progress_rows)
+    int64_t* __restrict__ progress_rows, float* __restrict__ poses)
 {
     constexpr int ARENA = B3 ? RS_B3_LDS_FLOATS : RS_LDS_FLOATS;
     __shared__ __attribute__((aligned(16))) float lds[ARENA + 32 + BM * MLP_NACT];
@@ -133,6 +152,7 @@ __global__ __launch_bounds__(THREADS, WPS) void rollout_all_kernel(
         __syncthreads();
         FlyRegs nx;
         fly_body<PH_ALL>(c, act, b, lds, blockIdx.x, st, &nx, in_lds ? acts : nullptr);
+        if (REC && blockIdx.x == 0) store_pose(poses, t, nx);
         st = nx;
         if (threadIdx.x < MLP_NACT && var_decay > 0.0f) varcur[threadIdx.x] = fmaxf(var_min, varcur[threadIdx.x] - var_decay);
         if (!in_lds) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // observation row t + 1 is in L2 before any wave of this workgroup reads it
@@ -148,14 +168,20 @@ __global__ __launch_bounds__(THREADS, WPS) void rollout_all_kernel(
 // policy and env halves (+ the 100 MHz real-time counter once, at [T][1]).
 // MULTI: more tiles than workgroups (> 8192 envs on 256 CUs): the outer loop really loops; the single-tile instantiation keeps
 // the register allocation of a kernel without it.
-template <bool STAMP, bool MULTI>
+// REC: the pose record of rollout_all_kernel (store_pose, workgroup 0's first tile), poses [T][FLY_POSE_FLOATS] in `aux`.
+template <bool STAMP, bool MULTI, bool REC>
 __global__ __launch_bounds__(THREADS, 1) void rollout_all_fs_kernel(
     const FlyConfig* __restrict__ c, FlyBuffers b, const float* __restrict__ P, const u16* __restrict__ PB,
     float* __restrict__ obs_ring, long n, const float* __restrict__ eps_all, const float* __restrict__ var, float var_decay,
     float var_min, float* __restrict__ act_all, float* __restrict__ logp_all, float* __restrict__ v_ring,
     float* __restrict__ reward_all, int T, int64_t* __restrict__ reset_rows, int64_t* __restrict__ progress_rows,
-    unsigned long long* __restrict__ stamps)
+    void* __restrict__ aux)
 {
+    // aux: the stamps (STAMP) or the pose record (REC) -- one slot, so that the kernel arguments, and with them the offsets of the
+    // implicit ones (gridDim), stay those of the kernel without recording
+    static_assert(!(STAMP && REC), "the stamped diagnostic form does not record");
+    unsigned long long* const stamps = static_cast<unsigned long long*>(aux);
+    float* const poses = static_cast<float*>(aux);
     extern __shared__ __attribute__((aligned(16))) u16 fr_lds[];
     const FrLds L(fr_lds);
     constexpr int PH_ALL = PH_SCALE | PH_RESET | PH_INTEGRATE | PH_OBS | PH_PROGRESS | PH_REWARD;
@@ -189,6 +215,7 @@ __global__ __launch_bounds__(THREADS, 1) void rollout_all_fs_kernel(
                                              // after the env step; not kept)
             FlyRegs nx;
             fly_body<PH_ALL>(c, act, b, L.obs, (int)tile, st, &nx, L.acts);
+            if (REC && tile == 0) store_pose(poses, t, nx);
             st = nx;
             if (threadIdx.x < MLP_NACT && var_decay > 0.0f) L.varcur[threadIdx.x] = fmaxf(var_min, L.varcur[threadIdx.x] - var_decay);
             __syncthreads();
@@ -201,12 +228,14 @@ __global__ __launch_bounds__(THREADS, 1) void rollout_all_fs_kernel(
 
 }  // namespace
 
+// poses (optional, device [T][FLY_POSE_FLOATS]): launch the REC instantiation of whichever kernel the shape selects -- recording
+// never changes the launch form.  The stamped diagnostic instantiation does not record.
 extern "C" hipError_t flyhip_launch_rollout_all(const FlyConfig* dcfg, const FlyBuffers* b, const float* P, const float* PF,
                                                 float* obs_ring, int64_t n, const float* eps_all, const float* var,
                                                 float var_decay, float var_min, float* act_all, float* logp_all, float* v_ring,
                                                 float* reward_all, int T, const int* rows_applied, const uint16_t* PB,
                                                 int64_t* reset_rows, int64_t* progress_rows, void* stream,
-                                                unsigned long long* stamps)
+                                                unsigned long long* stamps, float* poses)
 {
     const dim3 grid((unsigned)((n + BM - 1) / BM));
     int cus = 256;
@@ -215,31 +244,43 @@ extern "C" hipError_t flyhip_launch_rollout_all(const FlyConfig* dcfg, const Fly
     const dim3 grid_fs((unsigned)((int)grid.x <= cus ? (int)grid.x : cus));   // the fused-style kernel walks its tiles itself
     const char* fs_env = getenv("FLY_ROLLOUT_FS");               // read per launch: the tests flip it inside one process
     const bool fs_off = fs_env != nullptr && fs_env[0] == '0';
+    if (stamps && poses) return hipErrorInvalidValue;
+    const bool rec = poses != nullptr;
     if (PB && n % BM == 0 && !fs_off) {       // the policy body in the fused step's style (A/B: FLY_ROLLOUT_FS=0); persistent over tiles
         const bool multi = (int)grid.x > cus;
-        const int si = (stamps ? 1 : 0) + (multi ? 2 : 0);
-        const void* fn = si == 0 ? reinterpret_cast<const void*>(rollout_all_fs_kernel<false, false>)
-                       : si == 1 ? reinterpret_cast<const void*>(rollout_all_fs_kernel<true, false>)
-                       : si == 2 ? reinterpret_cast<const void*>(rollout_all_fs_kernel<false, true>)
-                                 : reinterpret_cast<const void*>(rollout_all_fs_kernel<true, true>);
+        const int si = (stamps ? 1 : 0) + (multi ? 2 : 0) + (rec ? 4 : 0);
+        const void* fn = si == 0 ? reinterpret_cast<const void*>(rollout_all_fs_kernel<false, false, false>)
+                       : si == 1 ? reinterpret_cast<const void*>(rollout_all_fs_kernel<true, false, false>)
+                       : si == 2 ? reinterpret_cast<const void*>(rollout_all_fs_kernel<false, true, false>)
+                       : si == 3 ? reinterpret_cast<const void*>(rollout_all_fs_kernel<true, true, false>)
+                       : si == 4 ? reinterpret_cast<const void*>(rollout_all_fs_kernel<false, false, true>)
+                                 : reinterpret_cast<const void*>(rollout_all_fs_kernel<false, true, true>);
         {       // (per launch: the attribute belongs to the CURRENT device)
             hipError_t ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BYTES);
             if (ea != hipSuccess) return ea;
         }
-#define RAFS_LAUNCH(S_, M_)                                                                                                           \
-        hipLaunchKernelGGL((rollout_all_fs_kernel<S_, M_>), grid_fs, dim3(THREADS), FR_LDS_BYTES, (hipStream_t)stream, dcfg, *b, P, PB,   \
-                           obs_ring, (long)n, eps_all, var, var_decay, var_min, act_all, logp_all, v_ring, reward_all, T, reset_rows,  \
-                           progress_rows, stamps)
-        if (si == 0) RAFS_LAUNCH(false, false); else if (si == 1) RAFS_LAUNCH(true, false);
-        else if (si == 2) RAFS_LAUNCH(false, true); else RAFS_LAUNCH(true, true);
+#define RAFS_LAUNCH(S_, M_, R_)                                                                                                       \
+        hipLaunchKernelGGL((rollout_all_fs_kernel<S_, M_, R_>), grid_fs, dim3(THREADS), FR_LDS_BYTES, (hipStream_t)stream, dcfg, *b, P, \
+                           PB, obs_ring, (long)n, eps_all, var, var_decay, var_min, act_all, logp_all, v_ring, reward_all, T,         \
+                           reset_rows, progress_rows, rec ? (void*)poses : (void*)stamps)
+        if (si == 0) RAFS_LAUNCH(false, false, false); else if (si == 1) RAFS_LAUNCH(true, false, false);
+        else if (si == 2) RAFS_LAUNCH(false, true, false); else if (si == 3) RAFS_LAUNCH(true, true, false);
+        else if (si == 4) RAFS_LAUNCH(false, false, true); else RAFS_LAUNCH(false, true, true);
 #undef RAFS_LAUNCH
         return hipGetLastError();
     }
     if (stamps) return hipErrorInvalidValue;        // only the fused-style kernel has a stamped instantiation
 #define RA_LAUNCH(B3_, WPS_, PF_)                                                                                                  \
-    hipLaunchKernelGGL((rollout_all_kernel<B3_, WPS_>), grid, dim3(THREADS), 0, (hipStream_t)stream, dcfg, *b, P, (const void*)PF_, \
-                       obs_ring, (long)n, eps_all, var, var_decay, var_min, act_all, logp_all, v_ring, reward_all, T, rows_applied, reset_rows, \
-                       progress_rows)
+    do {                                                                                                                           \
+        if (rec)                                                                                                                   \
+            hipLaunchKernelGGL((rollout_all_kernel<B3_, WPS_, true>), grid, dim3(THREADS), 0, (hipStream_t)stream, dcfg, *b, P,     \
+                               (const void*)PF_, obs_ring, (long)n, eps_all, var, var_decay, var_min, act_all, logp_all, v_ring,    \
+                               reward_all, T, rows_applied, reset_rows, progress_rows, poses);                                      \
+        else                                                                                                                       \
+            hipLaunchKernelGGL((rollout_all_kernel<B3_, WPS_, false>), grid, dim3(THREADS), 0, (hipStream_t)stream, dcfg, *b, P,    \
+                               (const void*)PF_, obs_ring, (long)n, eps_all, var, var_decay, var_min, act_all, logp_all, v_ring,    \
+                               reward_all, T, rows_applied, reset_rows, progress_rows, poses);                                      \
+    } while (0)
     if (PB) { if (one_per_cu) RA_LAUNCH(true, 1, PB); else RA_LAUNCH(true, 1, PB); }      // the bf16x3 body needs one wave per SIMD anyway
     else { if (one_per_cu) RA_LAUNCH(false, 1, PF); else RA_LAUNCH(false, 2, PF); }
 #undef RA_LAUNCH

@@ -6,6 +6,7 @@ attributes (`num_obs`, `num_act`, `obs_buf`, `reward_buf`, `reset_buf`, `progres
 (`step`, `reset`, `get_obs`, `get_reward`, `simulate`, `render`, `generate_video`, `exit`).  What
 was a chain of torch ops plus Isaac Gym calls per step is ONE kernel launch through the C ABI
 (`fly_step`, include/flyhip.h); the unfused methods launch the matching single-phase kernels.
+With `args.record`, rank 0 records env 0 (record.py).
 
 No Isaac Gym, no PhysX, no CPU path: the rigid-body model behind `simulate()` is the
 build-defined FlyDyn because the reference's physics is a closed binary.
@@ -85,6 +86,12 @@ class Fly:
         self.finished_count = torch.zeros(n, **f32)
         self._bufs = _lib.FlyBuffers()
         self._refresh_pointers()
+        # recording (fly.py:592-610): env 0, rank 0 only (record.py)
+        self.recorder = None
+        if getattr(args, "record", False) and int(getattr(args, "rank", 0) or 0) == 0:
+            from .record import Recorder
+            self.recorder = Recorder(self, getattr(args, "record_dir_name", None) or "recording",
+                                     getattr(args, "time_steps_per_recorded_frame", 2))
 
     # ------------------------------------------------------------------------------------------
     def _refresh_pointers(self):
@@ -127,8 +134,13 @@ class Fly:
     def step(self, actions):
         """fly.py:624-681 in one launch."""
         a = self._check_actions(actions)
+        rec = self.recorder
+        row = rec.next_ring_row() if rec is not None else 0
         _lib.check(self._lib.fly_step(self._handle, C.c_void_p(a.data_ptr()), C.byref(self._bufs),
                                       _lib.stream_ptr()), "fly_step")
+        if rec is not None:
+            rec.capture(row)
+            rec.reached(row, self.render_count)
         self.render_count += 1
 
     def set_actions(self, actions):
@@ -223,16 +235,22 @@ class Fly:
                 "progress_reward": self.potentials - self.prev_potentials, "leg_reward": legs}
 
     def render(self):
-        """fly.py:487-562: there is no viewer in this build (headless only)."""
-        return None
+        """fly.py:487-562: there is no viewer in this build.  Not recording: None.  Recording: the recorded view of env 0's
+        current state, uint8 [H, W, 3] (one synchronous fly_render)."""
+        if self.recorder is None:
+            return None
+        return self.recorder.render_now()
 
     def generate_video(self):
-        """fly.py:592-610: recording needs the Isaac Gym camera API; not available here."""
-        if getattr(self.args, "record", False):
-            print("recording is not supported by the MI355X build (no renderer)")
+        """fly.py:592-610: finish the recorded frames (record.py); an .mp4 when ffmpeg is on PATH."""
+        if self.recorder is not None:
+            return self.recorder.generate_video()
+        return None
 
     def exit(self):
         """fly.py:617-621."""
+        if self.recorder is not None:
+            self.recorder.close()
         if self._handle:
             torch.cuda.synchronize(self.device)
             _lib.check(self._lib.fly_destroy(self._handle), "fly_destroy")

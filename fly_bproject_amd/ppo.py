@@ -551,6 +551,8 @@ class PPO:
         if rc:
             _lib.check(rc, "rollout step")
         self._after_step(t)
+        if env.recorder is not None:
+            env.recorder.capture(t)                                 # env 0's pose after this step (captured with it in a graph)
         env.render_count += 1
 
     def _launch_rollout(self):
@@ -564,6 +566,13 @@ class PPO:
             n = int(self.args.num_envs)
             self._reset_rows = torch.zeros((T, n), dtype=torch.long, device=self.device)
             self._progress_rows = torch.zeros((T, n), dtype=torch.long, device=self.device)
+        rec = env.recorder
+        if rec is not None:
+            # the launch writes env 0's pose of step t to row t of the record: frames of rows the host has not reached are
+            # rendered first (none unless a rollout was cut short), then the record is (re)registered
+            rec.buffer(T)
+            rec.flush()
+            _lib.check(self._lib.fly_set_pose_record(env._handle, P(rec.poses.data_ptr())), "fly_set_pose_record")
         # env._bufs.reset / .progress point at the CURRENT flags (the env's own tensors, or the last row of the previous
         # rollout): the launch reads them once, then writes step t's flags to row t
         _lib.check(self._lib.ppo_rollout_all(
@@ -666,6 +675,10 @@ class PPO:
         end = self.env.end
         if self._fwd_args is None or self._args_infer_gemm != self.policy.gemm_infer:
             self._prepare_step_args()                               # (re)built when the inference arithmetic changes
+        rec = self.env.recorder
+        step_s = self.env.render_count                              # the env step this call runs (record.py)
+        if rec is not None:
+            rec.buffer(self.rollout_size)
         with torch.no_grad():
             if self.persistent_rollout:
                 if t == 0:
@@ -694,15 +707,21 @@ class PPO:
                         g = torch.cuda.CUDAGraph()
                         g.register_generator_state(self._gen)
                         torch.cuda.synchronize(self.device)
+                        count = self.env.render_count               # capturing runs no env step
                         with torch.cuda.graph(g):
                             for tt in range(self.rollout_size):
                                 self._launch_step(tt)
+                        self.env.render_count = count
                         self._graphs[key] = g
                     g.replay()
                 self.env.obs_buf, self.env.reward_buf = self._obs_rows[t + 1], self._reward_rows[t]
                 self.env._bufs.obs, self.env._bufs.reward = self._buf_ptrs[t]
                 self._after_step(t)
                 self.env.render_count += 1
+            if rec is not None:
+                rec.reached(t, step_s)
+                if t + 1 == self.rollout_size:
+                    rec.flush()                                     # before the next rollout overwrites the record
 
         if t + 1 == self.rollout_size:                              # ppo.py:240-252
             self._flush_bookkeeping()                               # the update reads the decayed variance
@@ -742,7 +761,7 @@ class PPO:
         torch.save({k: v.detach().clone().contiguous() for k, v in self.net.state_dict().items()}, path)
 
     def generate_video(self):
-        self.env.generate_video()
+        return self.env.generate_video()
 
     def exit(self):
         self._check_step_counter()

@@ -53,6 +53,7 @@ extern "C" {
 #define FLY_NUM_ABDOMEN 5
 #define FLY_NUM_CONTACT 11
 #define FLY_ROOT_DIM 13
+#define FLY_POSE_FLOATS 25   /* a recorded pose: root pos xyz | quat xyzw | 18 joint angles, DoF order */
 
 #define FLY_OK 0
 #define FLY_E_ARG (-1)      /* bad argument (null pointer, bad size, misalignment) */
@@ -268,6 +269,66 @@ int ppo_rollout_all(FlyHandle h, const FlyBuffers* b, const float* params, const
                     const float* eps_all, const float* var, float var_decay, float var_min, float* act_all,
                     float* logp_all, float* v_ring, float* reward_all, int32_t T, const int32_t* rows_applied,
                     const uint16_t* params_b3, int64_t* reset_rows, int64_t* progress_rows, void* stream);
+
+/*
+ * Recording (trainer.py --record): a pose record out of the persistent rollout, and an on-device renderer.
+ *
+ * fly_set_pose_record: poses f32 [T][FLY_POSE_FLOATS] (device, NULL = off) is kept in the handle; while it is set,
+ * ppo_rollout_all launches the recording instantiation of whichever kernel it selects (the launch form never changes)
+ * and that writes env 0's pose after every step t to poses[t]: root position (3), quaternion xyzw (4), the 18 joint
+ * angles in DoF order -- bit for bit what root[0][0:7] / dof_state[0][:][0] hold after step t in the per-step form
+ * (the state after the step's reset and integrate).  The buffer must hold T rows of every later ppo_rollout_all call.
+ * Recording reads state only: every other output of the launch is unchanged.
+ */
+int fly_set_pose_record(FlyHandle h, float* poses);
+
+/*
+ * fly_render: `frames` poses f32 [F][FLY_POSE_FLOATS] (device) -> rgba_out u32 [F][H][W] (device, R in the low byte,
+ * A = 255), row 0 at the top.  id_out (optional, u8 [F][H][W]) receives the primitive class of every pixel:
+ * FLY_RID_SKY 0, FLY_RID_GROUND 1, FLY_RID_BODY 2 (thorax, head), FLY_RID_ABDOMEN 3, FLY_RID_LEG0 + l (leg l, DoF order).
+ * Geometry from the handle's FlyConfig (mm, body frame): leg l is two capsules, attach -> knee -> tip, with the
+ * kinematics of the physics (psi = azimuth + sigma (q_c - pose_c), alpha = alpha0 + (q_f - pose_f),
+ * gamma = alpha + beta0 + (q_t - pose_t); knee = attach + (cos psi Lf cos alpha, sin psi Lf cos alpha, Lf sin alpha),
+ * tip = attach + (cos psi rho, sin psi rho, zeta)); the abdomen is spheres at abdomen_pts joined by capsules; the
+ * thorax an ellipsoid and the head a sphere (the FLY_R_* constants below); the ground plane z = 0 a checkerboard of
+ * FLY_R_CHECKER mm squares in two greys; the rest sky.  Camera: at (x, y, 0) + cam_offset for the root at (x, y, z),
+ * looking at (x, y, look_z), world z up, vertical field of view fov_y_deg, one ray through every pixel centre.
+ * Shading: Lambert with one directional light (FLY_R_LIGHT) plus FLY_R_AMBIENT, one hard shadow ray from every hit;
+ * sky unshaded; no anti-aliasing (deterministic).  Channels quantised as floor(clamp(c, 0, 1) * 255 + 0.5).
+ * 1 <= W, H <= 4096, 1 <= F <= 65535.
+ */
+typedef struct FlyRenderConfig {
+    int32_t width, height;
+    float fov_y_deg;
+    float cam_offset[3];
+    float look_z;
+} FlyRenderConfig;
+
+#define FLY_RID_SKY 0
+#define FLY_RID_GROUND 1
+#define FLY_RID_BODY 2
+#define FLY_RID_ABDOMEN 3
+#define FLY_RID_LEG0 4
+/* scene constants (mm / linear RGB in [0, 1]); tests/render_ref.py restates them */
+#define FLY_R_THORAX_AXES 0.60f, 0.40f, 0.35f   /* ellipsoid semi-axes, centred on the root */
+#define FLY_R_HEAD_CENTER 0.75f, 0.0f, 0.05f
+#define FLY_R_HEAD_RADIUS 0.28f
+#define FLY_R_ABDOMEN_SPHERE 0.24f             /* sphere radius at each abdomen point */
+#define FLY_R_ABDOMEN_LINK 0.18f               /* capsule radius between consecutive points */
+#define FLY_R_LEG_RADIUS 0.06f
+#define FLY_R_CHECKER 1.0f
+#define FLY_R_LIGHT 0.3f, 0.2f, 1.0f            /* direction TOWARDS the light (normalised by the renderer) */
+#define FLY_R_AMBIENT 0.35f
+#define FLY_R_SHADOW_BIAS 1e-3f                 /* shadow-ray origin offset along the normal */
+#define FLY_R_SKY_RGB 0.62f, 0.76f, 0.92f
+#define FLY_R_GROUND_RGB_A 0.58f, 0.58f, 0.58f
+#define FLY_R_GROUND_RGB_B 0.42f, 0.42f, 0.42f
+#define FLY_R_BODY_RGB 0.45f, 0.30f, 0.15f
+#define FLY_R_ABDOMEN_RGB 0.70f, 0.52f, 0.22f
+#define FLY_R_LEG_RGB 0.22f, 0.16f, 0.10f
+
+int fly_render(FlyHandle h, const float* poses, int32_t frames, const FlyRenderConfig* rc, uint32_t* rgba_out,
+               uint8_t* id_out, void* stream);
 
 
 /*

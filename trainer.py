@@ -6,6 +6,10 @@ Same flags (`--sim_device --compute_device_id --graphics_device_id --num_envs --
 `--rl_device` (accepted alias; the reference uses sim_device for both), `--variant`
 (bigGrav = fly.py, lowGrav = flyLowGrav.py), `--reward` (standing | walking), `--max_steps`
 (bounded runs; the reference loops until the viewer's E key), `--seed` and `--log_throughput` (env-steps/s on the score line).
+Recording (`--record True` or `--record_dir_name DIR`): rank 0 renders env 0 on the GPU every
+`--time_steps_per_recorded_frame` env steps to DIR/frame_%06d.png (fly_bproject_amd/record.py) and, when ffmpeg is on
+PATH, assembles DIR.mp4 at the end.  Unlike the reference, which records only with its viewer open, recording does not
+depend on `--headless`: this build has no viewer.
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N trainer.py ...`;
 each rank owns `--num_envs` envs on its own GPU.
 """
