@@ -8,6 +8,7 @@
 #include <stdarg.h>
 #include <new>
 #include "flyhip.h"
+#include "obs_norm.h"
 
 extern "C" hipError_t flyhip_launch_env(int phases, const FlyConfig* dcfg, int n, const float* actions,
                                         const FlyBuffers* b, void* stream);
@@ -103,7 +104,7 @@ extern "C" hipError_t flyhip_launch_rollout_all(const FlyConfig* dcfg, const Fly
                                                 float var_decay, float var_min, float* act_all, float* logp_all, float* v_ring,
                                                 float* reward_all, int T, const int* rows_applied, const uint16_t* PB,
                                                 int64_t* reset_rows, int64_t* progress_rows, void* stream,
-                                                unsigned long long* stamps, float* poses);
+                                                unsigned long long* stamps, float* poses, int norm);
 extern "C" hipError_t flyhip_launch_render(const FlyConfig* dcfg, const float* poses, int frames, const FlyRenderConfig* rc,
                                            uint32_t* rgba_out, uint8_t* id_out, void* stream);
 extern "C" hipError_t flyhip_launch_rollout_bookkeeping(const float* reward, int64_t rows, int64_t n, float* terms,
@@ -112,14 +113,19 @@ extern "C" hipError_t flyhip_launch_rollout_bookkeeping(const float* reward, int
 extern "C" hipError_t flyhip_launch_rollout_step(const FlyConfig* dcfg, const FlyBuffers* b, const float* P, const float* PF,
                                                  const float* x, int64_t n, const float* eps, const float* var, int var_steps,
                                                  float var_decay, float var_min, float* act, float* logp, float* v_out,
-                                                 const uint16_t* PB, const int* var_base, void* stream);
+                                                 const uint16_t* PB, const int* var_base, void* stream, int norm);
 extern "C" hipError_t flyhip_launch_adv_stats(const float* adv, int64_t n, float* stats, void* stream);
 extern "C" hipError_t flyhip_launch_adv_apply(float* adv, int64_t n, const float* totals, float count, float eps, void* stream);
+extern "C" hipError_t flyhip_launch_obs_norm_pass(const float* ring, int64_t rows, int64_t count_from, const float* table,
+                                                  float* out, double* sets, void* stream);
+extern "C" hipError_t flyhip_launch_obs_norm_merge(double* stats, float* table, const double* sets, int64_t k, float clip,
+                                                   void* stream);
 
 struct FlyEnv {
     FlyConfig host;
     FlyConfig* dev;
     float* poses;           // fly_set_pose_record (device [T][FLY_POSE_FLOATS], NULL = off)
+    const float* obs_norm;  // fly_set_obs_norm (device [FLY_OBS_NORM_TABLE], NULL = off); also in dev's slot (obs_norm.h)
 };
 
 namespace {
@@ -197,9 +203,11 @@ int fly_create(const FlyConfig* cfg, FlyHandle* out)
     h->host = *cfg;
     h->dev = nullptr;
     h->poses = nullptr;
-    hipError_t e = hipMalloc((void**)&h->dev, sizeof(FlyConfig));
+    h->obs_norm = nullptr;
+    hipError_t e = hipMalloc((void**)&h->dev, OBS_NORM_SLOT + sizeof(const float*));    // FlyConfig + the table slot
     if (e != hipSuccess) { delete h; return hip_fail(e, "hipMalloc(FlyConfig)"); }
     e = hipMemcpy(h->dev, cfg, sizeof(FlyConfig), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(reinterpret_cast<char*>(h->dev) + OBS_NORM_SLOT, 0, sizeof(const float*));
     if (e != hipSuccess) { (void)hipFree(h->dev); delete h; return hip_fail(e, "hipMemcpy(FlyConfig)"); }
     *out = h;
     return FLY_OK;
@@ -231,7 +239,8 @@ int ppo_rollout_step(FlyHandle h, const FlyBuffers* b, const float* params, cons
     int rc = check_buffers(b, PH_SCALE | PH_RESET | PH_INTEGRATE | PH_OBS | PH_PROGRESS | PH_REWARD);
     if (rc) return rc;
     hipError_t e = flyhip_launch_rollout_step(h->dev, b, params, params_frag, x, h->host.num_envs, eps, var, var_steps,
-                                              var_decay, var_min, act_out, logp_out, v_out, params_b3, var_steps_base, stream);
+                                              var_decay, var_min, act_out, logp_out, v_out, params_b3, var_steps_base, stream,
+                                              h->obs_norm != nullptr);
     if (e != hipSuccess) return hip_fail(e, "ppo_rollout_step launch");
     return FLY_OK;
 }
@@ -252,9 +261,11 @@ static int rollout_all_impl(FlyHandle h, const FlyBuffers* b, const float* param
     bb.obs = obs_ring; bb.reward = reward_all;              // checked as present; the kernel walks the rows itself
     int rc = check_buffers(&bb, PH_SCALE | PH_RESET | PH_INTEGRATE | PH_OBS | PH_PROGRESS | PH_REWARD);
     if (rc) return rc;
+    if (stamps && h->obs_norm) return fail(FLY_E_ARG, "the stamped rollout does not normalise observations (fly_set_obs_norm)");
     hipError_t e = flyhip_launch_rollout_all(h->dev, &bb, params, params_frag, obs_ring, h->host.num_envs, eps_all, var,
                                              var_decay, var_min, act_all, logp_all, v_ring, reward_all, T, rows_applied,
-                                             params_b3, reset_rows, progress_rows, stream, stamps, stamps ? nullptr : h->poses);
+                                             params_b3, reset_rows, progress_rows, stream, stamps, stamps ? nullptr : h->poses,
+                                             h->obs_norm != nullptr);
     if (e != hipSuccess) return hip_fail(e, "ppo_rollout_all launch");
     return FLY_OK;
 }
@@ -286,6 +297,37 @@ int fly_set_pose_record(FlyHandle h, float* poses)
     if (!h) return fail(FLY_E_ARG, "handle is null");
     if (reinterpret_cast<uintptr_t>(poses) & 3) return fail(FLY_E_ARG, "fly_set_pose_record: poses is not 4-byte aligned");
     h->poses = poses;
+    return FLY_OK;
+}
+
+int fly_set_obs_norm(FlyHandle h, const float* table)
+{
+    if (!h) return fail(FLY_E_ARG, "handle is null");
+    if (reinterpret_cast<uintptr_t>(table) & 3) return fail(FLY_E_ARG, "fly_set_obs_norm: table is not 4-byte aligned");
+    // synchronous: the slot holds the new pointer before any later launch on any stream reads it
+    hipError_t e = hipMemcpy(reinterpret_cast<char*>(h->dev) + OBS_NORM_SLOT, &table, sizeof(table), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return hip_fail(e, "fly_set_obs_norm");
+    h->obs_norm = table;
+    return FLY_OK;
+}
+
+int ppo_obs_norm_pass(const float* ring, int64_t rows, int64_t count_from, const float* table, float* out, double* sets,
+                      void* stream)
+{
+    if (!ring || !table || !out || !sets) return fail(FLY_E_ARG, "ppo_obs_norm_pass: null pointer");
+    if (rows <= 0 || count_from < 0 || count_from > rows) return fail(FLY_E_ARG, "ppo_obs_norm_pass: bad row range");
+    if (ring == out) return fail(FLY_E_ARG, "ppo_obs_norm_pass: out must not alias the ring");
+    hipError_t e = flyhip_launch_obs_norm_pass(ring, rows, count_from, table, out, sets, stream);
+    if (e != hipSuccess) return hip_fail(e, "ppo_obs_norm_pass launch");
+    return FLY_OK;
+}
+
+int ppo_obs_norm_merge(double* stats, float* table, const double* sets, int64_t k, float clip, void* stream)
+{
+    if (!stats || !table || !sets) return fail(FLY_E_ARG, "ppo_obs_norm_merge: null pointer");
+    if (k <= 0 || !(clip > 0.0f)) return fail(FLY_E_ARG, "ppo_obs_norm_merge: bad argument");
+    hipError_t e = flyhip_launch_obs_norm_merge(stats, table, sets, k, clip, stream);
+    if (e != hipSuccess) return hip_fail(e, "ppo_obs_norm_merge launch");
     return FLY_OK;
 }
 

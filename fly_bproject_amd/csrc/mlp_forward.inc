@@ -19,7 +19,9 @@ constexpr int FWD_LDS_FLOATS = LDS_A_FLOATS + LDS_B_FLOATS + LDS_C_FLOATS;
 
 // The body walks tiles first_tile, first_tile + tile_stride, ... (< ntiles) on the caller's LDS
 // arena.
-template <bool STAMP, bool COH = false>
+// NORM: the input rows are normalised (obs_norm_apply) under the table norm_tab (LDS, published by a barrier before the call)
+// on their way into LDS; the rows in HBM stay raw.
+template <bool STAMP, bool COH = false, bool NORM = false>
 __device__ __forceinline__ void forward_body(
     float* lds, const long first_tile, const long tile_stride,
     const float* __restrict__ P, const float* __restrict__ PF, const float* __restrict__ x, long n,
@@ -27,7 +29,8 @@ __device__ __forceinline__ void forward_body(
     float* __restrict__ h1_save, float* __restrict__ h2_save, float* __restrict__ h3_save,
     const float* __restrict__ smp_eps, const float* __restrict__ smp_var, float* __restrict__ smp_act,
     float* __restrict__ smp_logp, unsigned long long* __restrict__ stamps_base,
-    const int smp_var_steps = 0, const float smp_var_decay = 0.0f, const float smp_var_min = 0.0f)
+    const int smp_var_steps = 0, const float smp_var_decay = 0.0f, const float smp_var_min = 0.0f,
+    const float* norm_tab = nullptr)
 {
     unsigned long long* stamps = stamps_base;
     float* ldsA = lds;
@@ -65,7 +68,8 @@ __device__ __forceinline__ void forward_body(
                 for (int j = 0; j < 4; ++j) {
                     const int f = 4 * i4 + j;
                     const int rr = f / MLP_IN, cc = f - rr * MLP_IN;
-                    ldsB[rr * (MLP_IN_PAD + 4) + cc] = e[j];
+                    ldsB[rr * (MLP_IN_PAD + 4) + cc] =
+                        NORM ? obs_norm_apply(e[j], norm_tab[cc], norm_tab[MLP_IN + cc], norm_tab[2 * MLP_IN]) : e[j];
                 }
             }
         }
@@ -245,7 +249,8 @@ constexpr int FWD_B3_LDS_FLOATS = 2 * B3_TILE_FLOATS + LB4;      // two tiles + 
 
 // The body walks tiles first_tile, first_tile + tile_stride, ... (< ntiles) on the caller's LDS
 // arena.
-template <bool STAMP, bool COH = false>
+// NORM / norm_tab: as forward_body's.
+template <bool STAMP, bool COH = false, bool NORM = false>
 __device__ __forceinline__ void forward_body_b3(
     float* lds, const long first_tile, const long tile_stride,
     const float* __restrict__ P, const u16* __restrict__ PB, const float* __restrict__ x, long n,
@@ -254,7 +259,8 @@ __device__ __forceinline__ void forward_body_b3(
     const float* __restrict__ smp_eps, const float* __restrict__ smp_var, float* __restrict__ smp_act,
     float* __restrict__ smp_logp, unsigned long long* __restrict__ stamps_base,
     const int smp_var_steps = 0, const float smp_var_decay = 0.0f, const float smp_var_min = 0.0f,
-    const float* x_tile_lds = nullptr, float* act_tile_lds = nullptr, const bool biases_resident = false)
+    const float* x_tile_lds = nullptr, float* act_tile_lds = nullptr, const bool biases_resident = false,
+    const float* norm_tab = nullptr)
 {
     // biases_resident: an earlier call on the same arena has left b1 | b2 | b3 in `ldsBias` and nothing has touched them since
     // x_tile_lds (one-launch rollout): the FIRST tile's rows lie in LDS as fp32 [32][73] (the env step of the same workgroup left
@@ -305,7 +311,7 @@ __device__ __forceinline__ void forward_body_b3(
                     const int f = 4 * i4 + j;
                     const int rr = f / MLP_IN, cc = f - rr * MLP_IN;
                     u16 sa, sb, sc;
-                    split3(e[j], sa, sb, sc);
+                    split3(NORM ? obs_norm_apply(e[j], norm_tab[cc], norm_tab[MLP_IN + cc], norm_tab[2 * MLP_IN]) : e[j], sa, sb, sc);
                     u16* q = ldsB + rr * (MLP_IN_PAD + B3_PAD) + cc;
                     q[0] = sa; q[b3_plane<MLP_IN_PAD>()] = sb; q[2 * b3_plane<MLP_IN_PAD>()] = sc;
                 }

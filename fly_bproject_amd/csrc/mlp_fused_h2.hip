@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include "flyhip.h"
 #include "mlp_layout.h"
+#include "obs_norm.h"
 
 namespace {
 

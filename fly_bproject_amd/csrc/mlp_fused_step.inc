@@ -818,11 +818,13 @@ __device__ __forceinline__ void policy_tile_fs_head(WeightHeadT<2>& w1, const u1
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     gemm_prefetch_b3<MLP_IN_PAD>(w1, PB + MLP_OFF_PB1, 2 * wave, threadIdx.x & 63);
 }
-template <bool STAMP = false>
+// NORM: the observation block is normalised in place (obs_norm_apply) under norm_tab (LDS, published by an earlier barrier)
+// before it is converted; the env step writes the next raw block over it.
+template <bool STAMP = false, bool NORM = false>
 __device__ __forceinline__ void policy_tile_fs(const FrLds& L, const long tile, const u16* __restrict__ PB, const float* __restrict__ x,
                                                const long n, float* __restrict__ v_out, const float* __restrict__ smp_eps,
                                                float* __restrict__ smp_act, float* __restrict__ smp_logp, const WeightHeadT<2>& w1,
-                                               unsigned long long* stamps = nullptr)
+                                               unsigned long long* stamps = nullptr, const float* norm_tab = nullptr)
 {
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int tl = tid;
@@ -855,6 +857,13 @@ __device__ __forceinline__ void policy_tile_fs(const FrLds& L, const long tile, 
 #pragma unroll
         for (int o = 1; o < 32; o <<= 1) lg += __shfl_xor(lg, o, 32);
         if (tid == 0) L.hld[0] = lg;
+    }
+    if (NORM) {     // exactly the elements this thread's conversion reads (FsXStoreSlices' map), so no barrier stands between
+        float* row = L.obs + (tl >> 3) * FS_IN;
+        const int c0 = 12 * (tl & 7);
+#pragma unroll
+        for (int j = 0; j < 12; ++j)
+            if (c0 + j < FS_IN) row[c0 + j] = obs_norm_apply(row[c0 + j], norm_tab[c0 + j], norm_tab[FS_IN + c0 + j], norm_tab[2 * FS_IN]);
     }
     { FsXStoreSlices xc(L.obs, L.X, tl); xc.all(); }
     __syncthreads();

@@ -27,6 +27,7 @@
 #include <cstdlib>
 #include "flyhip.h"
 #include "mlp_layout.h"
+#include "obs_norm.h"
 
 namespace {
 
@@ -48,26 +49,35 @@ namespace {
 constexpr int RS_LDS_FLOATS = FWD_LDS_FLOATS > ENVS_PER_BLOCK * FLY_NUM_OBS ? FWD_LDS_FLOATS : ENVS_PER_BLOCK * FLY_NUM_OBS;
 constexpr int RS_B3_LDS_FLOATS = FWD_B3_LDS_FLOATS > ENVS_PER_BLOCK * FLY_NUM_OBS ? FWD_B3_LDS_FLOATS : ENVS_PER_BLOCK * FLY_NUM_OBS;
 static_assert(ENVS_PER_BLOCK == BM && BLOCK == THREADS, "one forward tile = one env block");
+constexpr int NORM_LDS_FLOATS = OBS_NORM_TABLE + 1;     // the NORM instantiations' copy of the normalisation table (obs_norm.h)
+static_assert(MLP_IN == OBS_NORM_COLS && OBS_NORM_TABLE <= THREADS, "one table entry per thread");
 
 // B3: the policy body on the bf16 matrix pipe (three-term splits; PF then points at the term planes)
-template <bool B3>
+// NORM: the policy input is normalised under the table registered with the handle (fly_set_obs_norm, read through `c`)
+template <bool B3, bool NORM = false>
 __global__ __launch_bounds__(THREADS, B3 ? 1 : 2) void rollout_step_kernel(
     const FlyConfig* __restrict__ c, FlyBuffers b, const float* __restrict__ P, const void* __restrict__ PF,
     const float* __restrict__ x, long n, const float* __restrict__ eps, const float* __restrict__ var, int var_steps,
     float var_decay, float var_min, float* __restrict__ act, float* __restrict__ logp, float* __restrict__ v_out,
     const int* __restrict__ var_base)
 {
-    __shared__ __attribute__((aligned(16))) float lds[B3 ? RS_B3_LDS_FLOATS : RS_LDS_FLOATS];
+    constexpr int ARENA = B3 ? RS_B3_LDS_FLOATS : RS_LDS_FLOATS;
+    __shared__ __attribute__((aligned(16))) float lds[ARENA + (NORM ? NORM_LDS_FLOATS : 0)];
+    float* const norm_tab = NORM ? lds + ARENA : nullptr;
+    if (NORM) obs_norm_load(norm_tab, c);
     var_steps -= var_base ? *var_base : 0;                  // pending decays: frozen row index minus what is already applied
     constexpr int PH_ALL = PH_SCALE | PH_RESET | PH_INTEGRATE | PH_OBS | PH_PROGRESS | PH_REWARD;
     FlyRegs st;
     fly_load<PH_ALL>(st, c, b, blockIdx.x);                 // the env state's HBM round trip hides under the forward
+    if (NORM) __syncthreads();                              // publishes the table
     if (B3)
-        forward_body_b3<false>(lds, blockIdx.x, 1L << 40, P, static_cast<const u16*>(PF), x, n, nullptr, v_out, nullptr, nullptr,
-                               nullptr, nullptr, eps, var, act, logp, nullptr, var_steps, var_decay, var_min);
+        forward_body_b3<false, false, NORM>(lds, blockIdx.x, 1L << 40, P, static_cast<const u16*>(PF), x, n, nullptr, v_out, nullptr,
+                                            nullptr, nullptr, nullptr, eps, var, act, logp, nullptr, var_steps, var_decay, var_min,
+                                            nullptr, nullptr, false, norm_tab);
     else
-        forward_body<false>(lds, blockIdx.x, 1L << 40, P, static_cast<const float*>(PF), x, n, nullptr, v_out, nullptr, nullptr,
-                            nullptr, nullptr, eps, var, act, logp, nullptr, var_steps, var_decay, var_min);
+        forward_body<false, false, NORM>(lds, blockIdx.x, 1L << 40, P, static_cast<const float*>(PF), x, n, nullptr, v_out, nullptr,
+                                         nullptr, nullptr, nullptr, eps, var, act, logp, nullptr, var_steps, var_decay, var_min,
+                                         norm_tab);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_s_waitcnt(0);          // this thread's action stores are acknowledged by L2
     __syncthreads();
@@ -103,7 +113,8 @@ __device__ __forceinline__ void store_pose(float* __restrict__ poses, int t, con
 // WPS = waves per SIMD the registers are budgeted for: 1 when the launch has at most one workgroup per CU (<= 8192
 // envs: the step body plus the carried env state want ~300 registers and spill at 256), 2 beyond that.
 // REC: store env 0's pose of every step to poses [T][FLY_POSE_FLOATS] (store_pose); the other instantiations ignore `poses`.
-template <bool B3, int WPS, bool REC>
+// NORM: the policy input of every step is normalised (rollout_step_kernel's NORM); the observation ring stays raw.
+template <bool B3, int WPS, bool REC, bool NORM = false>
 __global__ __launch_bounds__(THREADS, WPS) void rollout_all_kernel(
     const FlyConfig* __restrict__ c, FlyBuffers b, const float* __restrict__ P, const void* __restrict__ PF,
     float* __restrict__ obs_ring, long n, const float* __restrict__ eps_all, const float* __restrict__ var, float var_decay,
@@ -112,7 +123,9 @@ __global__ __launch_bounds__(THREADS, WPS) void rollout_all_kernel(
     int64_t* __restrict__ progress_rows, float* __restrict__ poses)
 {
     constexpr int ARENA = B3 ? RS_B3_LDS_FLOATS : RS_LDS_FLOATS;
-    __shared__ __attribute__((aligned(16))) float lds[ARENA + 32 + BM * MLP_NACT];
+    __shared__ __attribute__((aligned(16))) float lds[ARENA + 32 + BM * MLP_NACT + (NORM ? NORM_LDS_FLOATS : 0)];
+    float* const norm_tab = NORM ? lds + ARENA + 32 + BM * MLP_NACT : nullptr;
+    if (NORM) obs_norm_load(norm_tab, c);                        // published by the barrier below
     constexpr int PH_ALL = PH_SCALE | PH_RESET | PH_INTEGRATE | PH_OBS | PH_PROGRESS | PH_REWARD;
     // the variance of the CURRENT row lives in LDS and is decayed once per step (ppo.py:236-237): the same sequence of
     // fp32 operations as the per-step form, O(1) per step however long the rollout (T = 40 960 at 16 envs)
@@ -137,14 +150,14 @@ __global__ __launch_bounds__(THREADS, WPS) void rollout_all_kernel(
         if (reset_rows) { b.reset = reset_rows + (long)t * n; b.progress = progress_rows + (long)t * n; }   // fly.py:175-177, per step
         const bool in_lds = B3 && whole;
         if (B3)
-            forward_body_b3<false>(lds, blockIdx.x, 1L << 40, P, static_cast<const u16*>(PF), x, n, nullptr, v_ring + (long)t * n,
-                                   nullptr, nullptr, nullptr, nullptr, eps_all + (long)t * n * MLP_NACT, varcur, act,
-                                   logp_all + (long)t * n, nullptr, 0, var_decay, var_min,
-                                   in_lds && t > 0 ? lds : nullptr, in_lds ? acts : nullptr, t > 0);
+            forward_body_b3<false, false, NORM>(lds, blockIdx.x, 1L << 40, P, static_cast<const u16*>(PF), x, n, nullptr,
+                                                v_ring + (long)t * n, nullptr, nullptr, nullptr, nullptr, eps_all + (long)t * n * MLP_NACT,
+                                                varcur, act, logp_all + (long)t * n, nullptr, 0, var_decay, var_min,
+                                                in_lds && t > 0 ? lds : nullptr, in_lds ? acts : nullptr, t > 0, norm_tab);
         else
-            forward_body<false>(lds, blockIdx.x, 1L << 40, P, static_cast<const float*>(PF), x, n, nullptr, v_ring + (long)t * n,
-                                nullptr, nullptr, nullptr, nullptr, eps_all + (long)t * n * MLP_NACT, varcur, act,
-                                logp_all + (long)t * n, nullptr, 0, var_decay, var_min);
+            forward_body<false, false, NORM>(lds, blockIdx.x, 1L << 40, P, static_cast<const float*>(PF), x, n, nullptr,
+                                             v_ring + (long)t * n, nullptr, nullptr, nullptr, nullptr, eps_all + (long)t * n * MLP_NACT,
+                                             varcur, act, logp_all + (long)t * n, nullptr, 0, var_decay, var_min, norm_tab);
         if (!in_lds) {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             __builtin_amdgcn_s_waitcnt(0);      // this thread's action stores are acknowledged by L2
@@ -169,7 +182,9 @@ __global__ __launch_bounds__(THREADS, WPS) void rollout_all_kernel(
 // MULTI: more tiles than workgroups (> 8192 envs on 256 CUs): the outer loop really loops; the single-tile instantiation keeps
 // the register allocation of a kernel without it.
 // REC: the pose record of rollout_all_kernel (store_pose, workgroup 0's first tile), poses [T][FLY_POSE_FLOATS] in `aux`.
-template <bool STAMP, bool MULTI, bool REC>
+// NORM: the observation block is normalised before its conversion (policy_tile_fs); the table sits behind the FR_LDS_BYTES of
+// the image (the launch asks for NORM_LDS_FLOATS more).
+template <bool STAMP, bool MULTI, bool REC, bool NORM = false>
 __global__ __launch_bounds__(THREADS, 1) void rollout_all_fs_kernel(
     const FlyConfig* __restrict__ c, FlyBuffers b, const float* __restrict__ P, const u16* __restrict__ PB,
     float* __restrict__ obs_ring, long n, const float* __restrict__ eps_all, const float* __restrict__ var, float var_decay,
@@ -179,13 +194,15 @@ __global__ __launch_bounds__(THREADS, 1) void rollout_all_fs_kernel(
 {
     // aux: the stamps (STAMP) or the pose record (REC) -- one slot, so that the kernel arguments, and with them the offsets of the
     // implicit ones (gridDim), stay those of the kernel without recording
-    static_assert(!(STAMP && REC), "the stamped diagnostic form does not record");
+    static_assert(!(STAMP && REC) && !(STAMP && NORM), "the stamped diagnostic form neither records nor normalises");
     unsigned long long* const stamps = static_cast<unsigned long long*>(aux);
     float* const poses = static_cast<float*>(aux);
     extern __shared__ __attribute__((aligned(16))) u16 fr_lds[];
     const FrLds L(fr_lds);
     constexpr int PH_ALL = PH_SCALE | PH_RESET | PH_INTEGRATE | PH_OBS | PH_PROGRESS | PH_REWARD;
     policy_tile_fs_setup(L, P);
+    float* const norm_tab = NORM ? reinterpret_cast<float*>(fr_lds) + FR_LDS_BYTES / 4 : nullptr;
+    if (NORM) obs_norm_load(norm_tab, c);                     // published, like the biases, by the barrier before step 0
     int64_t* const reset0 = b.reset;                          // the CURRENT flags: read once per tile, before the tile's step 0
     int64_t* const progress0 = b.progress;
     const long ntiles = n / BM;                               // whole tiles only (the launcher checks)
@@ -208,8 +225,8 @@ __global__ __launch_bounds__(THREADS, 1) void rollout_all_fs_kernel(
             b.obs = obs_ring + (long)(t + 1) * n * FLY_NUM_OBS;
             b.reward = reward_all + (long)t * n;
             if (reset_rows) { b.reset = reset_rows + (long)t * n; b.progress = progress_rows + (long)t * n; }   // fly.py:175-177, per step
-            policy_tile_fs<STAMP>(L, tile, PB, t == 0 ? obs_ring : nullptr, n, v_ring + (long)t * n, eps_all + (long)t * n * MLP_NACT, act,
-                                  logp_all + (long)t * n, w1, STAMP ? st_tile + 8 * t : nullptr);
+            policy_tile_fs<STAMP, NORM>(L, tile, PB, t == 0 ? obs_ring : nullptr, n, v_ring + (long)t * n, eps_all + (long)t * n * MLP_NACT,
+                                        act, logp_all + (long)t * n, w1, STAMP ? st_tile + 8 * t : nullptr, norm_tab);
             stamp<STAMP>(st_tile, 8 * t + 7);
             policy_tile_fs_head(w1, PB);     // the NEXT step's first weights: their round trip hides under the physics (A/B: requested
                                              // after the env step; not kept)
@@ -228,14 +245,32 @@ __global__ __launch_bounds__(THREADS, 1) void rollout_all_fs_kernel(
 
 }  // namespace
 
+// the normalising instantiations of rollout_all_fs_kernel (the table is read through dcfg: the argument list is the plain one's)
+template <bool MULTI, bool REC>
+static hipError_t launch_rollout_all_fs_norm(dim3 grid, hipStream_t stream, const FlyConfig* dcfg, const FlyBuffers* b, const float* P,
+                                             const uint16_t* PB, float* obs_ring, long n, const float* eps_all, const float* var,
+                                             float var_decay, float var_min, float* act_all, float* logp_all, float* v_ring,
+                                             float* reward_all, int T, int64_t* reset_rows, int64_t* progress_rows, void* aux)
+{
+    const int bytes = FR_LDS_BYTES + NORM_LDS_FLOATS * 4;
+    static_assert(FR_LDS_BYTES % 4 == 0, "the table follows the image");
+    hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(rollout_all_fs_kernel<false, MULTI, REC, true>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (ea != hipSuccess) return ea;
+    hipLaunchKernelGGL((rollout_all_fs_kernel<false, MULTI, REC, true>), grid, dim3(THREADS), bytes, stream, dcfg, *b, P, PB, obs_ring,
+                       n, eps_all, var, var_decay, var_min, act_all, logp_all, v_ring, reward_all, T, reset_rows, progress_rows, aux);
+    return hipGetLastError();
+}
+
 // poses (optional, device [T][FLY_POSE_FLOATS]): launch the REC instantiation of whichever kernel the shape selects -- recording
-// never changes the launch form.  The stamped diagnostic instantiation does not record.
+// never changes the launch form.  The stamped diagnostic instantiation does not record.  norm: the NORM instantiation of the same
+// kernel (the table registered in dcfg's slot, fly_set_obs_norm); not with stamps.
 extern "C" hipError_t flyhip_launch_rollout_all(const FlyConfig* dcfg, const FlyBuffers* b, const float* P, const float* PF,
                                                 float* obs_ring, int64_t n, const float* eps_all, const float* var,
                                                 float var_decay, float var_min, float* act_all, float* logp_all, float* v_ring,
                                                 float* reward_all, int T, const int* rows_applied, const uint16_t* PB,
                                                 int64_t* reset_rows, int64_t* progress_rows, void* stream,
-                                                unsigned long long* stamps, float* poses)
+                                                unsigned long long* stamps, float* poses, int norm)
 {
     const dim3 grid((unsigned)((n + BM - 1) / BM));
     int cus = 256;
@@ -244,10 +279,17 @@ extern "C" hipError_t flyhip_launch_rollout_all(const FlyConfig* dcfg, const Fly
     const dim3 grid_fs((unsigned)((int)grid.x <= cus ? (int)grid.x : cus));   // the fused-style kernel walks its tiles itself
     const char* fs_env = getenv("FLY_ROLLOUT_FS");               // read per launch: the tests flip it inside one process
     const bool fs_off = fs_env != nullptr && fs_env[0] == '0';
-    if (stamps && poses) return hipErrorInvalidValue;
+    if (stamps && (poses || norm)) return hipErrorInvalidValue;
     const bool rec = poses != nullptr;
     if (PB && n % BM == 0 && !fs_off) {       // the policy body in the fused step's style (A/B: FLY_ROLLOUT_FS=0); persistent over tiles
         const bool multi = (int)grid.x > cus;
+        if (norm) {
+#define RAFS_NORM(M_, R_) launch_rollout_all_fs_norm<M_, R_>(grid_fs, (hipStream_t)stream, dcfg, b, P, PB, obs_ring, (long)n, eps_all, var, \
+                                                             var_decay, var_min, act_all, logp_all, v_ring, reward_all, T, reset_rows,    \
+                                                             progress_rows, poses)
+            return multi ? (rec ? RAFS_NORM(true, true) : RAFS_NORM(true, false)) : (rec ? RAFS_NORM(false, true) : RAFS_NORM(false, false));
+#undef RAFS_NORM
+        }
         const int si = (stamps ? 1 : 0) + (multi ? 2 : 0) + (rec ? 4 : 0);
         const void* fn = si == 0 ? reinterpret_cast<const void*>(rollout_all_fs_kernel<false, false, false>)
                        : si == 1 ? reinterpret_cast<const void*>(rollout_all_fs_kernel<true, false, false>)
@@ -272,7 +314,15 @@ extern "C" hipError_t flyhip_launch_rollout_all(const FlyConfig* dcfg, const Fly
     if (stamps) return hipErrorInvalidValue;        // only the fused-style kernel has a stamped instantiation
 #define RA_LAUNCH(B3_, WPS_, PF_)                                                                                                  \
     do {                                                                                                                           \
-        if (rec)                                                                                                                   \
+        if (norm && rec)                                                                                                           \
+            hipLaunchKernelGGL((rollout_all_kernel<B3_, WPS_, true, true>), grid, dim3(THREADS), 0, (hipStream_t)stream, dcfg, *b, \
+                               P, (const void*)PF_, obs_ring, (long)n, eps_all, var, var_decay, var_min, act_all, logp_all, v_ring, \
+                               reward_all, T, rows_applied, reset_rows, progress_rows, poses);                                      \
+        else if (norm)                                                                                                             \
+            hipLaunchKernelGGL((rollout_all_kernel<B3_, WPS_, false, true>), grid, dim3(THREADS), 0, (hipStream_t)stream, dcfg, *b,\
+                               P, (const void*)PF_, obs_ring, (long)n, eps_all, var, var_decay, var_min, act_all, logp_all, v_ring, \
+                               reward_all, T, rows_applied, reset_rows, progress_rows, poses);                                      \
+        else if (rec)                                                                                                              \
             hipLaunchKernelGGL((rollout_all_kernel<B3_, WPS_, true>), grid, dim3(THREADS), 0, (hipStream_t)stream, dcfg, *b, P,     \
                                (const void*)PF_, obs_ring, (long)n, eps_all, var, var_decay, var_min, act_all, logp_all, v_ring,    \
                                reward_all, T, rows_applied, reset_rows, progress_rows, poses);                                      \
@@ -432,10 +482,16 @@ extern "C" int flyhip_debug_mlp_fwd_bwd_stamped(const float* P, const float* PF,
 extern "C" hipError_t flyhip_launch_rollout_step(const FlyConfig* dcfg, const FlyBuffers* b, const float* P, const float* PF,
                                                  const float* x, int64_t n, const float* eps, const float* var, int var_steps,
                                                  float var_decay, float var_min, float* act, float* logp, float* v_out,
-                                                 const uint16_t* PB, const int* var_base, void* stream)
+                                                 const uint16_t* PB, const int* var_base, void* stream, int norm)
 {
     const dim3 grid((unsigned)((n + BM - 1) / BM));
-    if (PB)
+    if (norm && PB)
+        hipLaunchKernelGGL((rollout_step_kernel<true, true>), grid, dim3(THREADS), 0, (hipStream_t)stream, dcfg, *b, P, (const void*)PB,
+                           x, (long)n, eps, var, var_steps, var_decay, var_min, act, logp, v_out, var_base);
+    else if (norm)
+        hipLaunchKernelGGL((rollout_step_kernel<false, true>), grid, dim3(THREADS), 0, (hipStream_t)stream, dcfg, *b, P, (const void*)PF,
+                           x, (long)n, eps, var, var_steps, var_decay, var_min, act, logp, v_out, var_base);
+    else if (PB)
         hipLaunchKernelGGL(rollout_step_kernel<true>, grid, dim3(THREADS), 0, (hipStream_t)stream, dcfg, *b, P, (const void*)PB,
                            x, (long)n, eps, var, var_steps, var_decay, var_min, act, logp, v_out, var_base);
     else

@@ -186,7 +186,12 @@ def broadcast_parameters(module, src=0):
 
 def broadcast_policy(agent, src=0):
     """Replicate rank `src`'s policy: ONE broadcast of the packed parameter buffer, then rebuild
-    the fragment-ordered copies the kernels stream."""
+    the fragment-ordered copies the kernels stream.  With observation normalisation, the running
+    statistics and the table the kernels read go along (a checkpoint loaded on rank 0 reaches
+    every rank)."""
     if dist.is_initialized() and dist.get_world_size() > 1:
         dist.broadcast(agent.policy.P, src=src)
         agent.policy.refresh()
+        if getattr(agent, "normalize_obs", False):
+            dist.broadcast(agent._obs_stats, src=src)
+            dist.broadcast(agent._obs_table, src=src)

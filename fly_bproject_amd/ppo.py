@@ -66,6 +66,38 @@ def diag_gauss_logprob(mu, action, var):
     return -0.5 * (mu.shape[-1] * 1.8378770664093453 + M) - half_log_det
 
 
+OBS_RMS_KEYS = ("obs_rms.mean", "obs_rms.var", "obs_rms.count")
+
+
+def split_obs_rms(state_dict, normalize_obs):
+    """Remove the observation statistics (obs_rms.*) from a loaded state dict, in place, and return them: the rest then loads
+    strictly into Net (a reference checkpoint has none).  Statistics without `normalize_obs` are an error: the network was
+    trained on normalised inputs."""
+    rms = {k: state_dict.pop(k) for k in list(state_dict) if k.startswith("obs_rms.")}
+    if rms and not normalize_obs:
+        raise ValueError("this checkpoint was trained with observation normalisation (it holds %s): run with --normalize_obs"
+                         % ", ".join(sorted(rms)))
+    if rms and sorted(rms) != sorted(OBS_RMS_KEYS):
+        raise ValueError("incomplete observation statistics in the checkpoint: %s (want %s)" % (sorted(rms), list(OBS_RMS_KEYS)))
+    return rms
+
+
+def obs_norm_table(stats, clip):
+    """The table the kernels read, from S = count | mean[k] | var[k] (float64): m = (float) mean, r = (float) (1 / sqrt(var +
+    1e-5)), clip -- each rounded once from float64 (what ppo_obs_norm_merge writes)."""
+    k = (stats.numel() - 1) // 2
+    mean, var = stats[1:1 + k].double(), stats[1 + k:].double()
+    return torch.cat((mean.float(), (1.0 / torch.sqrt(var + 1e-5)).float(),
+                      torch.full((1,), clip, dtype=torch.float32, device=stats.device)))
+
+
+def normalize_obs_ref(x, table):
+    """torch's statement of the kernels' normalisation: ((x - m) * r).clamp(-clip, clip), NaN passing through."""
+    k = (table.numel() - 1) // 2
+    clip = float(table[2 * k])
+    return ((x - table[:k]) * table[k:2 * k]).clamp(-clip, clip)
+
+
 class PPO:
     def __init__(self, args, env=None):
         self.args = args
@@ -110,6 +142,12 @@ class PPO:
         self._mu = torch.zeros((n, self.num_acts), device=dev)
         self.normalize_advantage = bool(getattr(args, "normalize_advantage", False))
         self._adv_stats = torch.zeros(514, device=dev)
+        # opt-in (`normalize_obs`, rl_games' normalize_input): the policy sees clamp((obs - mean) * rsqrt(var + 1e-5), +-obs_clip)
+        # under running statistics of the observations.  The ring keeps the raw rows; see _setup_obs_norm.
+        self.normalize_obs = bool(getattr(args, "normalize_obs", False))
+        self.obs_clip = float(getattr(args, "obs_clip", 5.0))
+        if self.normalize_obs and not self.obs_clip > 0.0:
+            raise ValueError("obs_clip must be > 0 (got %r)" % self.obs_clip)
         self.use_graph = bool(getattr(args, "graph", False))
         # one launch per ROLLOUT (ppo_rollout_all): each workgroup loops over the T steps of its own 32 envs.  The device then
         # runs ahead of the host's step count inside a rollout, but everything `run()` reads per step is a ROW the launch wrote
@@ -149,9 +187,12 @@ class PPO:
         self.optim_step = 0
 
         self.net = Net(self.env.num_obs, self.env.num_act).to(dev)
+        loaded_rms = {}
         if getattr(self.args, "load", False):                       # ppo.py:147-149
             print("loaded from: ", str(self.args.load_path))
-            self.net.load_state_dict(torch.load(self.args.load_path, map_location=dev, weights_only=True))
+            sd = torch.load(self.args.load_path, map_location=dev, weights_only=True)
+            loaded_rms = split_obs_rms(sd, self.normalize_obs)
+            self.net.load_state_dict(sd)
         self._loaded = bool(getattr(self.args, "load", False))
         from .policy import PackedPolicy
         self.policy = PackedPolicy(self.net, dev)                   # parameters become views of one packed buffer
@@ -171,6 +212,9 @@ class PPO:
         self.optim = torch.optim.Adam(self.net.parameters(), lr=self.lr)
 
         self._lib = _lib.load()
+        self._obs_norm_ring = None
+        if self.normalize_obs:
+            self._setup_obs_norm(loaded_rms)
         self._gen = torch.Generator(device=dev)
         self._gen.manual_seed(int(getattr(args, "seed", 0)) + 1000003 * int(getattr(args, "rank", 0)))
         self.world_size = int(getattr(args, "world_size", 1))
@@ -190,6 +234,68 @@ class PPO:
         if self.world_size > 1:
             from .dist import FlatGradAllReduce
             self._flat_grad = FlatGradAllReduce(self.net.parameters(), self.world_size)
+
+    # ------------------------------------------------------------------------------------------
+    # observation normalisation (opt-in)
+    def _setup_obs_norm(self, loaded_rms):
+        """The running statistics S (f64: count | mean[73] | var[73], initially 0 | 0 | 1), the table the kernels read (f32:
+        m[73] | r[73] | clip, derived from S), the normalised copy of the ring, the pass's moment sets; the table is registered
+        with the env handle, so every rollout launch from here on normalises its policy input.  The table's address never
+        changes: the merge rewrites it in place (captured graphs stay valid)."""
+        dev, k = self.device, self.num_obs
+        self._obs_stats = torch.zeros(_lib.OBS_NORM_SET, dtype=torch.float64, device=dev)
+        self._obs_stats[1 + k:] = 1.0
+        if loaded_rms:
+            self._obs_stats[0] = loaded_rms["obs_rms.count"].to(dev, torch.float64).reshape(())
+            self._obs_stats[1:1 + k] = loaded_rms["obs_rms.mean"].to(dev, torch.float64)
+            self._obs_stats[1 + k:] = loaded_rms["obs_rms.var"].to(dev, torch.float64)
+        elif getattr(self.args, "load", False):
+            print("normalize_obs: %s holds no observation statistics (obs_rms.*); starting from mean 0, var 1"
+                  % str(self.args.load_path))
+        self._obs_table = torch.empty(_lib.OBS_NORM_SET, dtype=torch.float32, device=dev)
+        self._obs_table.copy_(obs_norm_table(self._obs_stats, self.obs_clip))
+        self._obs_norm_ring = torch.empty_like(self._obs_ring)
+        self._obs_sets = torch.zeros((_lib.OBS_NORM_SETS, _lib.OBS_NORM_SET), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)                                 # the table is in place before any launch reads it
+        _lib.check(self._lib.fly_set_obs_norm(self.env._handle, C.c_void_p(self._obs_table.data_ptr())), "fly_set_obs_norm")
+
+    @property
+    def obs_mean(self):
+        """Running mean of the observations (f64 [73], a copy), or None when normalisation is off."""
+        return self._obs_stats[1:1 + self.num_obs].clone() if self.normalize_obs else None
+
+    @property
+    def obs_var(self):
+        """Running population variance of the observations (f64 [73], a copy), or None when normalisation is off."""
+        return self._obs_stats[1 + self.num_obs:].clone() if self.normalize_obs else None
+
+    @property
+    def obs_count(self):
+        """Rows the running statistics are taken over (f64 scalar, a copy), or None when normalisation is off."""
+        return self._obs_stats[0].clone() if self.normalize_obs else None
+
+    def _obs_norm_pass(self):
+        """ppo_obs_norm_pass over the whole ring: rows 0..T normalised under the current table into _obs_norm_ring, and the
+        float64 moments of rows 1..T (the observations this rollout produced; row 0 is the previous rollout's row T) into
+        _obs_sets.  Idempotent until the next merge."""
+        T, n = self.rollout_size, int(self.args.num_envs)
+        p = lambda x: C.c_void_p(x.data_ptr())   # noqa: E731
+        _lib.check(self._lib.ppo_obs_norm_pass(p(self._obs_ring), C.c_int64((T + 1) * n), C.c_int64(n), p(self._obs_table),
+                                               p(self._obs_norm_ring), p(self._obs_sets), _lib.stream_ptr()), "ppo_obs_norm_pass")
+
+    def _merge_obs_stats(self):
+        """Fold the moments of the last pass into S (all ranks' sets, in rank order) and rewrite the table: S_k -> S_k+1."""
+        sets = self._obs_sets
+        if self.world_size > 1:
+            import torch.distributed as dist
+            src = sets.cpu() if dist.get_backend() == "gloo" else sets
+            parts = [torch.empty_like(src) for _ in range(self.world_size)]
+            dist.all_gather(parts, src)
+            sets = torch.cat(parts).to(self.device)
+            self._keep_sets = sets                                  # alive until the stream has consumed it
+        p = lambda x: C.c_void_p(x.data_ptr())   # noqa: E731
+        _lib.check(self._lib.ppo_obs_norm_merge(p(self._obs_stats), p(self._obs_table), p(sets), C.c_int64(sets.shape[0]),
+                                                C.c_float(self.obs_clip), _lib.stream_ptr()), "ppo_obs_norm_merge")
 
     # ppo.py:230 replaces the whole [T,N,1] buffer by the LAST step's [N,1] mask after every step
     # (Q1).  reset_buf only changes inside env.step, so deriving the mask on demand is the same
@@ -249,11 +355,15 @@ class PPO:
         broadcast over T (Q1), and the recurrence never resets at episode ends (Q2)."""
         T, n = self.rollout_size, self.args.num_envs
         with torch.no_grad():
+            ring = self._obs_ring
+            if self.normalize_obs:
+                self._obs_norm_pass()                               # the rows the rollout's policy saw, under the same table
+                ring = self._obs_norm_ring
             if self.reuse_rollout_values and self._v_have == T and self._v_version == self.policy.version:
-                self._v_ring[T].copy_(self.net.v(self._obs_ring[T]))
+                self._v_ring[T].copy_(self.net.v(ring[T]))
                 values = self._v_ring                               # rows 0..T-1 were written by the rollout launches
             else:
-                values = self.net.v(self._obs_ring)                 # [T+1, N, 1]: v(obs) and v(next_obs) in one pass
+                values = self.net.v(ring)                           # [T+1, N, 1]: v(obs) and v(next_obs) in one pass
             self._v_have = 0
             done = self.all_done
             per_step = done.dim() == 3 and done.shape[0] == T and done.shape[1] == n
@@ -270,7 +380,8 @@ class PPO:
             self._keep = (values, done_f)                           # alive until the stream has consumed them
             if self.normalize_advantage:
                 self._normalize_advantage()
-        return self.all_obs, self.all_acts, self.all_log_prob, self._target, self.all_advantage
+        obs = self._obs_norm_ring[:T] if self.normalize_obs else self.all_obs
+        return obs, self.all_acts, self.all_log_prob, self._target, self.all_advantage
 
     def _normalize_advantage(self):
         """Opt-in (`normalize_advantage`): adv <- (adv - mean) / (std + 1e-8) over the whole rollout of
@@ -305,7 +416,13 @@ class PPO:
             self._flush_bookkeeping()                               # the loss uses the variance after this rollout's decays
         obs, action, old_log_prob, target, advantage = self.make_data()
         if self.update_backend == "hip":
-            return self._update_hip(obs, action, old_log_prob, target, advantage)
+            self._update_hip(obs, action, old_log_prob, target, advantage)
+        else:
+            self._update_torch(obs, action, old_log_prob, target, advantage)
+        if self.normalize_obs:
+            self._merge_obs_stats()                                 # after update k: the statistics of rollout k + 1
+
+    def _update_torch(self, obs, action, old_log_prob, target, advantage):
         for _ in range(self.epoch):
             k = 0
             for j in range(self.mini_chunk_size, self.rollout_size, self.mini_chunk_size):
@@ -530,6 +647,9 @@ class PPO:
         # two-launch form (mlp_forward_sample + fly_step) for the A/B test
         self.fuse_rollout_step = os.environ.get("FLY_FUSE_ROLLOUT_STEP", "1") != "0"
         self._args_infer_gemm = pol.gemm_infer
+        if self.normalize_obs and not self.fuse_rollout_step and not self.persistent_rollout:
+            raise _lib.FlyHipError("normalize_obs: the two-launch rollout step (FLY_FUSE_ROLLOUT_STEP=0, mlp_forward_sample) does not "
+                                   "normalise observations; use the one-launch step")
 
     def _launch_step(self, t):
         """The device work of one env step (ppo.py:213-237): ONE launch (`ppo_rollout_step`), no host logic.  Rows of
@@ -758,7 +878,10 @@ class PPO:
             return
         path = self.args.save_path + endofname + ".pth"
         # parameters are views of the packed buffer: save compact, contiguous copies
-        torch.save({k: v.detach().clone().contiguous() for k, v in self.net.state_dict().items()}, path)
+        sd = {k: v.detach().clone().contiguous() for k, v in self.net.state_dict().items()}
+        if self.normalize_obs:                                      # only then: otherwise the file is the reference's
+            sd["obs_rms.mean"], sd["obs_rms.var"], sd["obs_rms.count"] = self.obs_mean, self.obs_var, self.obs_count
+        torch.save(sd, path)
 
     def generate_video(self):
         return self.env.generate_video()

@@ -54,6 +54,9 @@ extern "C" {
 #define FLY_NUM_CONTACT 11
 #define FLY_ROOT_DIM 13
 #define FLY_POSE_FLOATS 25   /* a recorded pose: root pos xyz | quat xyzw | 18 joint angles, DoF order */
+#define FLY_OBS_NORM_TABLE 147   /* observation normalisation table: mean[73] | rstd[73] | clip (f32) */
+#define FLY_OBS_NORM_SET 147     /* one set of statistics or moments: count | mean[73] | var or M2[73] (f64) */
+#define FLY_OBS_NORM_SETS 256    /* moment sets ppo_obs_norm_pass writes (one per workgroup) */
 
 #define FLY_OK 0
 #define FLY_E_ARG (-1)      /* bad argument (null pointer, bad size, misalignment) */
@@ -183,6 +186,27 @@ int ppo_td_gae(const float* reward, const float* v, const float* v_next, const f
  *   the global count. */
 int ppo_adv_stats(const float* adv, int64_t n, float* stats, void* stream);
 int ppo_adv_apply(float* adv, int64_t n, const float* totals, float count, float eps, void* stream);
+
+/* Running observation normalisation (opt-in, PPO --normalize_obs).
+ *   table f32 [FLY_OBS_NORM_TABLE] = m[73] | r[73] | clip; a kernel input x of column j becomes
+ *     y = clamp((x - m_j) * r_j, -clip, clip), two separately rounded fp32 ops and a clamp that lets NaN through
+ *     (torch's ((x - m) * r).clamp(-clip, clip), bit for bit).
+ *   stats f64 [FLY_OBS_NORM_SET] = count | mean[73] | population var[73]: the running statistics (initially 0 | 0 | 1).
+ *
+ * ppo_obs_norm_pass: ring f32 [rows][73] -> out f32 [rows][73] (normalised under `table`; out must not alias ring), and
+ *   the float64 moments (count | mean[73] | M2[73]) of rows >= count_from, one set per workgroup in
+ *   sets f64 [FLY_OBS_NORM_SETS][FLY_OBS_NORM_SET] (sets over no counted row have count 0).  Deterministic.
+ * ppo_obs_norm_merge: combines sets[0 .. k-1] in order (Chan's parallel update; empty sets are skipped), folds the
+ *   result into `stats` and rewrites table's m / r from it in float64, rounded once (r = 1 / sqrt(var + 1e-5)), and
+ *   table[146] = clip.  One workgroup, no host sync; data-parallel callers gather every rank's sets and pass them in
+ *   rank order, so all ranks hold bit-identical statistics.
+ * fly_set_obs_norm: registers `table` (device, NULL = off) with the handle.  While it is set, ppo_rollout_all and
+ *   ppo_rollout_step launch the normalising instantiation of the kernel they select: the policy sees the normalised
+ *   input, the env still writes raw observations.  The table is read at every launch, so it may change between them. */
+int ppo_obs_norm_pass(const float* ring, int64_t rows, int64_t count_from, const float* table, float* out, double* sets,
+                      void* stream);
+int ppo_obs_norm_merge(double* stats, float* table, const double* sets, int64_t k, float clip, void* stream);
+int fly_set_obs_norm(FlyHandle h, const float* table);
 
 /* ppo.py:233 and :237 without the per-step host sync: *score_acc += mean(reward) * score_scale;
  * action_var[j] = max(var_min, action_var[j] - var_decay) (skipped when var_decay <= 0). */

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Does the loop learn?  Runs ITERS PPO iterations at N envs and prints, per iteration, the mean
 per-step reward of the rollout and the episode statistics (mean return / length of finished
-episodes).  Usage: python tools/train_curve.py [ITERS] [N] [backend] [variant] [gemm: f16x2 (default) | bf16x3 | f32]"""
+episodes).  Usage: python tools/train_curve.py [ITERS] [N] [backend] [variant] [gemm: f16x2 (default) | bf16x3 | f32] [norm]
+`norm` as the sixth argument turns on observation normalisation (--normalize_obs)."""
 import contextlib
 import io
 import os
@@ -18,13 +19,15 @@ iters = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 8192
 backend = sys.argv[3] if len(sys.argv) > 3 else "hip"
 variant = sys.argv[4] if len(sys.argv) > 4 else "bigGrav"
-gemm = sys.argv[5] if len(sys.argv) > 5 else None
+gemm = sys.argv[5] if len(sys.argv) > 5 and sys.argv[5] != "-" else None
+norm = len(sys.argv) > 6 and sys.argv[6] == "norm"
 torch.manual_seed(0)
 with contextlib.redirect_stdout(io.StringIO()):
-    agent = PPO(make_args(n, update_backend=backend, variant=variant))
+    agent = PPO(make_args(n, update_backend=backend, variant=variant, normalize_obs=norm))
     if gemm:
         agent.policy.gemm = gemm
-print("arithmetic: gemm=%s step_gemm=%s (%s)" % (agent.policy.gemm, agent.policy.step_gemm, agent.policy.update_path()))
+print("arithmetic: gemm=%s step_gemm=%s (%s) normalize_obs=%s" % (agent.policy.gemm, agent.policy.step_gemm, agent.policy.update_path(),
+                                                                  norm))
 t0 = time.perf_counter()
 for it in range(iters):
     with contextlib.redirect_stdout(io.StringIO()):

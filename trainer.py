@@ -6,6 +6,9 @@ Same flags (`--sim_device --compute_device_id --graphics_device_id --num_envs --
 `--rl_device` (accepted alias; the reference uses sim_device for both), `--variant`
 (bigGrav = fly.py, lowGrav = flyLowGrav.py), `--reward` (standing | walking), `--max_steps`
 (bounded runs; the reference loops until the viewer's E key), `--seed` and `--log_throughput` (env-steps/s on the score line).
+`--normalize_obs` (running mean / std normalisation of the policy input, rl_games' normalize_input; off by default) with
+`--obs_clip` (the bound of a normalised input, default 5.0): the statistics are saved with the checkpoint as obs_rms.* and
+loaded with it; such a checkpoint needs `--normalize_obs` to load.
 Recording (`--record True` or `--record_dir_name DIR`): rank 0 renders env 0 on the GPU every
 `--time_steps_per_recorded_frame` env steps to DIR/frame_%06d.png (fly_bproject_amd/record.py) and, when ffmpeg is on
 PATH, assembles DIR.mp4 at the end.  Unlike the reference, which records only with its viewer open, recording does not
@@ -55,6 +58,10 @@ def parse_args(argv=None):
                              'batch) or average parameters once per PPO update (non-parity)')
     parser.add_argument('--normalize_advantage', action='store_true',
                         help='normalise advantages over the rollout (not in the reference; off by default)')
+    parser.add_argument('--normalize_obs', action='store_true',
+                        help='normalise the policy input by running mean / std of the observations, clamped to +-obs_clip '
+                             '(rl_games normalize_input; not in the reference; off by default)')
+    parser.add_argument('--obs_clip', type=float, default=5.0, help='bound of a normalised observation (with --normalize_obs)')
     args = parser.parse_args(argv)
     if args.save_path is not None:          # trainer.py:27-34
         args.save = True
