@@ -24,9 +24,15 @@ class FlyRenderConfig(C.Structure):
                 ("look_z", C.c_float)]
 
 
+class FlyRandomization(C.Structure):
+    _fields_ = [("lo", C.c_float * 6), ("hi", C.c_float * 6), ("seed", C.c_uint32), ("reserved", C.c_int32)]
+
+
 POSE_FLOATS = 25        # FLY_POSE_FLOATS: root pos xyz | quat xyzw | 18 joint angles
 OBS_NORM_SET = 147      # FLY_OBS_NORM_SET / FLY_OBS_NORM_TABLE: count | mean[73] | var or M2[73] (f64); m[73] | r[73] | clip (f32)
 OBS_NORM_SETS = 256     # FLY_OBS_NORM_SETS: moment sets one ppo_obs_norm_pass writes
+DR_PARAMS = 6           # FLY_DR_PARAMS: kp, kd, effort, mass (+ inertia), mu, gravity multipliers
+DR_ROW = 8              # FLY_DR_ROW: a randomisation table row, f32 m[6] | draw count (int32 bits) | 0
 ABI_VERSION = 13        # include/flyhip.h as this package binds it (fly_abi_version(): argument lists changed between versions)
 # name -> argtypes; every entry point returns int except fly_last_error
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
@@ -42,6 +48,7 @@ SYMBOLS = {
     "fly_pack_reward": [_P, C.POINTER(FlyBuffers), _I, _P],
     "fly_set_pose_record": [_P, _P],
     "fly_set_obs_norm": [_P, _P],
+    "fly_set_randomization": [_P, C.POINTER(FlyRandomization), _P, _P],
     "fly_render": [_P, _P, _I, C.POINTER(FlyRenderConfig), _P, _P, _P],
     "ppo_sample_logprob": [_P, _P, _P, _P, _P, _L, _P],
     "ppo_td_gae": [_P, _P, _P, _P, _F, _F, _L, _L, _P, _P, _I, _P],

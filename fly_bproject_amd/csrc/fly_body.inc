@@ -138,15 +138,20 @@ __device__ __forceinline__ float scale_action(float a, float lo, float hi)
 // `obs_tile`: LDS scratch of ENVS_PER_BLOCK * 73 floats; `block`: index of this workgroup's 32 envs.
 // The per-lane slice of an env's state, loaded before the body runs: the one-launch rollout step requests
 // it BEFORE the policy forward so the HBM round trip hides under the MFMAs.
+// dm / dk: the DR instantiations' copy of the env's table row (domain_rand.h): multipliers and draw count.  The persistent
+// rollout kernels carry them from step to step like the rest; the plain instantiations never touch them.
 struct FlyRegs {
     Root r;
     float jq[3], jqd[3];
     float pot, prev_pot;
     int rs;
     long progress;
+    float dm[FLY_DR_PARAMS];
+    uint32_t dk;
 };
 
-template <int PH>
+// DR: per-env physics domain randomisation (fly_set_randomization): the phases that reset or integrate read the env's row
+template <int PH, bool DR = false>
 __device__ __forceinline__ void fly_load(FlyRegs& st, const FlyConfig* __restrict__ c, const FlyBuffers& b, const int block)
 {
     const int n = c->num_envs;
@@ -181,11 +186,15 @@ __device__ __forceinline__ void fly_load(FlyRegs& st, const FlyConfig* __restric
     if (NEED_FLAG) st.rs = (int)(b.reset[e] != 0);
     st.progress = 0;
     if (NEED_PROG) st.progress = b.progress[e];
+    if constexpr (DR && (PH & (PH_RESET | PH_INTEGRATE)) != 0) dr_load_row(c, e, st.dm, st.dk);
 }
 
 // `st_out` (optional): the state the step leaves, back in registers -- the one-launch-per-ROLLOUT kernel carries it
 // from step to step instead of re-reading what it has just stored.
-template <int PH>
+// DR: FlyDyn runs on the env's multiplied constants (st.dm), and every reset draws the env's next row, which one lane stores
+// (tail lanes that shadow env n - 1 do not): before the physics when resets come first, so that the new draw drives this
+// step; after it with reset_after_sim, so that it applies from the next step.
+template <int PH, bool DR = false>
 __device__ __forceinline__ void fly_body(const FlyConfig* __restrict__ c, const float* __restrict__ actions, const FlyBuffers& b,
                                          float* obs_tile, const int block, const FlyRegs& st, FlyRegs* st_out = nullptr,
                                          const float* actions_tile = nullptr)
@@ -216,6 +225,14 @@ __device__ __forceinline__ void fly_body(const FlyConfig* __restrict__ c, const 
     float pot = st.pot, prev_pot = st.prev_pot;
     int rs = st.rs;
     long progress = st.progress;
+    float dm[FLY_DR_PARAMS];
+    uint32_t dk = 0;
+    bool drew = false;
+    if constexpr (DR) {
+#pragma unroll
+        for (int j = 0; j < FLY_DR_PARAMS; ++j) dm[j] = st.dm[j];
+        dk = st.dk;
+    }
     float cf[3] = {0, 0, 0};   // this lane's leg-tip contact force (lanes 0..5)
     float cfa[3] = {0, 0, 0};  // this lane's abdomen-point contact force (lanes 0..4)
 
@@ -257,6 +274,11 @@ __device__ __forceinline__ void fly_body(const FlyConfig* __restrict__ c, const 
             float p = -nrm / c->dt;
             prev_pot = p; pot = p;
             rs = 0; progress = 0;
+            if constexpr (DR) {
+                dr_draw(c, (uint32_t)e, dk, dm);
+                dk += 1u;
+                drew = true;
+            }
         }
     };
 
@@ -266,12 +288,16 @@ __device__ __forceinline__ void fly_body(const FlyConfig* __restrict__ c, const 
     if (PH & PH_INTEGRATE) {
         const int nsub = c->substeps;
         const float h = c->dt / (float)nsub;
-        const float kp = c->kp, kd = c->kd, eff = c->effort, vmax = c->vmax, Jinv = 1.0f / c->joint_inertia;
-        const float minv = 1.0f / c->mass, g = c->gravity;
-        const float I0 = c->inertia[0], I1 = c->inertia[1], I2 = c->inertia[2];
+        // DR: the env's constants, one fp32 product each, formed once per env step (the substep loop is the plain one)
+        const float kp = DR ? __fmul_rn(c->kp, dm[0]) : c->kp, kd = DR ? __fmul_rn(c->kd, dm[1]) : c->kd;
+        const float eff = DR ? __fmul_rn(c->effort, dm[2]) : c->effort, vmax = c->vmax, Jinv = 1.0f / c->joint_inertia;
+        const float minv = 1.0f / (DR ? __fmul_rn(c->mass, dm[3]) : c->mass), g = DR ? __fmul_rn(c->gravity, dm[5]) : c->gravity;
+        const float I0 = DR ? __fmul_rn(c->inertia[0], dm[3]) : c->inertia[0];
+        const float I1 = DR ? __fmul_rn(c->inertia[1], dm[3]) : c->inertia[1];
+        const float I2 = DR ? __fmul_rn(c->inertia[2], dm[3]) : c->inertia[2];
         const float I0inv = 1.0f / I0, I1inv = 1.0f / I1, I2inv = 1.0f / I2;
         const float vlim = c->max_lin_vel, wlim = c->max_ang_vel;
-        const float kc = c->kc, cd = c->cdamp, mu = c->mu, cv = c->cvisc;
+        const float kc = c->kc, cd = c->cdamp, mu = DR ? __fmul_rn(c->mu, dm[4]) : c->mu, cv = c->cvisc;
         const float Lf = c->femur_len, Lt = c->tibia_len;
         const float ld = 1.0f - h * c->lin_damp, ad = 1.0f - h * c->ang_damp;
         const float att0 = c->leg_attach[leg][0], att1 = c->leg_attach[leg][1], att2 = c->leg_attach[leg][2];
@@ -497,9 +523,17 @@ __device__ __forceinline__ void fly_body(const FlyConfig* __restrict__ c, const 
 #pragma unroll
         for (int i = 0; i < 3; ++i) { st_out->jq[i] = jq[i]; st_out->jqd[i] = jqd[i]; }
         st_out->pot = pot; st_out->prev_pot = prev_pot; st_out->rs = rs; st_out->progress = progress;
+        if constexpr (DR) {
+#pragma unroll
+            for (int j = 0; j < FLY_DR_PARAMS; ++j) st_out->dm[j] = dm[j];
+            st_out->dk = dk;
+        }
     }
     // ---- store --------------------------------------------------------------------------------
     if (!valid) return;
+    if constexpr (DR) {
+        if (drew && sub == 0) dr_store_row(c, e, dm, dk);
+    }
     if (PH & (PH_SCALE)) {
         if (is_leg) {
             float* tp = b.targets + e * FLY_NUM_DOF + j0;

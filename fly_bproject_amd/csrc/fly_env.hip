@@ -25,6 +25,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "flyhip.h"
+#include "domain_rand.h"
 
 namespace {
 
@@ -40,6 +41,18 @@ __global__ __launch_bounds__(BLOCK) void fly_kernel(const FlyConfig* __restrict_
     fly_body<PH>(c, actions, b, obs_tile, blockIdx.x, st);
 }
 
+// the randomising instantiations (fly_set_randomization) of the phase sets that reset or integrate; a kernel of its own name so
+// that the plain fly_kernel<PH> keep theirs
+template <int PH>
+__global__ __launch_bounds__(BLOCK) void fly_dr_kernel(const FlyConfig* __restrict__ c,
+                                                       const float* __restrict__ actions, FlyBuffers b)
+{
+    __shared__ __attribute__((aligned(16))) float obs_tile[ENVS_PER_BLOCK * FLY_NUM_OBS];
+    FlyRegs st;
+    fly_load<PH, true>(st, c, b, blockIdx.x);
+    fly_body<PH, true>(c, actions, b, obs_tile, blockIdx.x, st);
+}
+
 inline int grid_for(int n) { return (n + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK; }
 
 }  // namespace
@@ -49,9 +62,24 @@ inline int grid_for(int n) { return (n + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK; }
     hipLaunchKernelGGL((fly_kernel<PH>), dim3(grid_for(n)), dim3(BLOCK), 0, (hipStream_t)stream, \
                        dcfg, actions, *b)
 
+#define FLY_DR_LAUNCH(PH)                                                                            \
+    hipLaunchKernelGGL((fly_dr_kernel<PH>), dim3(grid_for(n)), dim3(BLOCK), 0, (hipStream_t)stream, \
+                       dcfg, actions, *b)
+
+// dr: launch the randomising instantiation (the table registered in dcfg's slot); the phase sets that neither reset nor integrate
+// have none and run the plain kernel
 extern "C" hipError_t flyhip_launch_env(int phases, const FlyConfig* dcfg, int n, const float* actions,
-                                        const FlyBuffers* b, void* stream)
+                                        const FlyBuffers* b, void* stream, int dr)
 {
+    if (dr) {
+        switch (phases) {
+        case PH_SCALE | PH_RESET | PH_INTEGRATE | PH_OBS | PH_PROGRESS | PH_REWARD:
+            FLY_DR_LAUNCH(PH_SCALE | PH_RESET | PH_INTEGRATE | PH_OBS | PH_PROGRESS | PH_REWARD); return hipGetLastError();
+        case PH_RESET: FLY_DR_LAUNCH(PH_RESET); return hipGetLastError();
+        case PH_INTEGRATE: FLY_DR_LAUNCH(PH_INTEGRATE); return hipGetLastError();
+        default: break;
+        }
+    }
     switch (phases) {
     case PH_SCALE | PH_RESET | PH_INTEGRATE | PH_OBS | PH_PROGRESS | PH_REWARD:
         FLY_LAUNCH(PH_SCALE | PH_RESET | PH_INTEGRATE | PH_OBS | PH_PROGRESS | PH_REWARD); break;

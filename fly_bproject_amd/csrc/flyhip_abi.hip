@@ -9,9 +9,11 @@
 #include <new>
 #include "flyhip.h"
 #include "obs_norm.h"
+#include "domain_rand.h"
+#include <math.h>
 
 extern "C" hipError_t flyhip_launch_env(int phases, const FlyConfig* dcfg, int n, const float* actions,
-                                        const FlyBuffers* b, void* stream);
+                                        const FlyBuffers* b, void* stream, int dr);
 extern "C" hipError_t flyhip_launch_sample_logprob(const float* mu, const float* var, const float* eps,
                                                    float* act_out, float* logp_out, int64_t n, void* stream);
 extern "C" hipError_t flyhip_launch_td_gae(const float* reward, const float* v, const float* v_next,
@@ -104,7 +106,7 @@ extern "C" hipError_t flyhip_launch_rollout_all(const FlyConfig* dcfg, const Fly
                                                 float var_decay, float var_min, float* act_all, float* logp_all, float* v_ring,
                                                 float* reward_all, int T, const int* rows_applied, const uint16_t* PB,
                                                 int64_t* reset_rows, int64_t* progress_rows, void* stream,
-                                                unsigned long long* stamps, float* poses, int norm);
+                                                unsigned long long* stamps, float* poses, int norm, int dr);
 extern "C" hipError_t flyhip_launch_render(const FlyConfig* dcfg, const float* poses, int frames, const FlyRenderConfig* rc,
                                            uint32_t* rgba_out, uint8_t* id_out, void* stream);
 extern "C" hipError_t flyhip_launch_rollout_bookkeeping(const float* reward, int64_t rows, int64_t n, float* terms,
@@ -113,19 +115,21 @@ extern "C" hipError_t flyhip_launch_rollout_bookkeeping(const float* reward, int
 extern "C" hipError_t flyhip_launch_rollout_step(const FlyConfig* dcfg, const FlyBuffers* b, const float* P, const float* PF,
                                                  const float* x, int64_t n, const float* eps, const float* var, int var_steps,
                                                  float var_decay, float var_min, float* act, float* logp, float* v_out,
-                                                 const uint16_t* PB, const int* var_base, void* stream, int norm);
+                                                 const uint16_t* PB, const int* var_base, void* stream, int norm, int dr);
 extern "C" hipError_t flyhip_launch_adv_stats(const float* adv, int64_t n, float* stats, void* stream);
 extern "C" hipError_t flyhip_launch_adv_apply(float* adv, int64_t n, const float* totals, float count, float eps, void* stream);
 extern "C" hipError_t flyhip_launch_obs_norm_pass(const float* ring, int64_t rows, int64_t count_from, const float* table,
                                                   float* out, double* sets, void* stream);
 extern "C" hipError_t flyhip_launch_obs_norm_merge(double* stats, float* table, const double* sets, int64_t k, float clip,
                                                    void* stream);
+extern "C" hipError_t flyhip_launch_dr_register(const FlyConfig* dcfg, int n, void* stream);
 
 struct FlyEnv {
     FlyConfig host;
     FlyConfig* dev;
     float* poses;           // fly_set_pose_record (device [T][FLY_POSE_FLOATS], NULL = off)
     const float* obs_norm;  // fly_set_obs_norm (device [FLY_OBS_NORM_TABLE], NULL = off); also in dev's slot (obs_norm.h)
+    float* dr_table;        // fly_set_randomization (device [N][FLY_DR_ROW], NULL = off); with the ranges in dev's slot (domain_rand.h)
 };
 
 namespace {
@@ -175,7 +179,7 @@ int launch(FlyHandle h, int phases, const float* actions, const FlyBuffers* b, v
     if ((phases & PH_SCALE) && !actions) return fail(FLY_E_ARG, "actions is null");
     int rc = check_buffers(b, phases);
     if (rc) return rc;
-    hipError_t e = flyhip_launch_env(phases, h->dev, h->host.num_envs, actions, b, stream);
+    hipError_t e = flyhip_launch_env(phases, h->dev, h->host.num_envs, actions, b, stream, h->dr_table != nullptr);
     if (e != hipSuccess) return hip_fail(e, "fly env kernel launch");
     return FLY_OK;
 }
@@ -204,10 +208,11 @@ int fly_create(const FlyConfig* cfg, FlyHandle* out)
     h->dev = nullptr;
     h->poses = nullptr;
     h->obs_norm = nullptr;
-    hipError_t e = hipMalloc((void**)&h->dev, OBS_NORM_SLOT + sizeof(const float*));    // FlyConfig + the table slot
+    h->dr_table = nullptr;
+    hipError_t e = hipMalloc((void**)&h->dev, DR_CONFIG_BYTES);    // FlyConfig + the obs-norm table slot + the randomisation slot
     if (e != hipSuccess) { delete h; return hip_fail(e, "hipMalloc(FlyConfig)"); }
     e = hipMemcpy(h->dev, cfg, sizeof(FlyConfig), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(reinterpret_cast<char*>(h->dev) + OBS_NORM_SLOT, 0, sizeof(const float*));
+    if (e == hipSuccess) e = hipMemset(reinterpret_cast<char*>(h->dev) + OBS_NORM_SLOT, 0, DR_CONFIG_BYTES - OBS_NORM_SLOT);
     if (e != hipSuccess) { (void)hipFree(h->dev); delete h; return hip_fail(e, "hipMemcpy(FlyConfig)"); }
     *out = h;
     return FLY_OK;
@@ -240,7 +245,7 @@ int ppo_rollout_step(FlyHandle h, const FlyBuffers* b, const float* params, cons
     if (rc) return rc;
     hipError_t e = flyhip_launch_rollout_step(h->dev, b, params, params_frag, x, h->host.num_envs, eps, var, var_steps,
                                               var_decay, var_min, act_out, logp_out, v_out, params_b3, var_steps_base, stream,
-                                              h->obs_norm != nullptr);
+                                              h->obs_norm != nullptr, h->dr_table != nullptr);
     if (e != hipSuccess) return hip_fail(e, "ppo_rollout_step launch");
     return FLY_OK;
 }
@@ -262,10 +267,11 @@ static int rollout_all_impl(FlyHandle h, const FlyBuffers* b, const float* param
     int rc = check_buffers(&bb, PH_SCALE | PH_RESET | PH_INTEGRATE | PH_OBS | PH_PROGRESS | PH_REWARD);
     if (rc) return rc;
     if (stamps && h->obs_norm) return fail(FLY_E_ARG, "the stamped rollout does not normalise observations (fly_set_obs_norm)");
+    if (stamps && h->dr_table) return fail(FLY_E_ARG, "the stamped rollout does not randomise the physics (fly_set_randomization)");
     hipError_t e = flyhip_launch_rollout_all(h->dev, &bb, params, params_frag, obs_ring, h->host.num_envs, eps_all, var,
                                              var_decay, var_min, act_all, logp_all, v_ring, reward_all, T, rows_applied,
                                              params_b3, reset_rows, progress_rows, stream, stamps, stamps ? nullptr : h->poses,
-                                             h->obs_norm != nullptr);
+                                             h->obs_norm != nullptr, h->dr_table != nullptr);
     if (e != hipSuccess) return hip_fail(e, "ppo_rollout_all launch");
     return FLY_OK;
 }
@@ -308,6 +314,34 @@ int fly_set_obs_norm(FlyHandle h, const float* table)
     hipError_t e = hipMemcpy(reinterpret_cast<char*>(h->dev) + OBS_NORM_SLOT, &table, sizeof(table), hipMemcpyHostToDevice);
     if (e != hipSuccess) return hip_fail(e, "fly_set_obs_norm");
     h->obs_norm = table;
+    return FLY_OK;
+}
+
+int fly_set_randomization(FlyHandle h, const FlyRandomization* r, float* env_params, void* stream)
+{
+    if (!h) return fail(FLY_E_ARG, "handle is null");
+    if (!r) {               // off: the plain kernels again; the slot and the table are left as they are
+        h->dr_table = nullptr;
+        return FLY_OK;
+    }
+    static const char* const names[FLY_DR_PARAMS] = {"kp", "kd", "effort", "mass", "mu", "gravity"};
+    for (int j = 0; j < FLY_DR_PARAMS; ++j) {
+        const float lo = r->lo[j], hi = r->hi[j];
+        if (!isfinite(lo) || !isfinite(hi)) return fail(FLY_E_ARG, "fly_set_randomization: %s bounds are not finite", names[j]);
+        if (!(lo > 0.0f)) return fail(FLY_E_ARG, "fly_set_randomization: %s lower bound must be > 0 (got %g)", names[j], (double)lo);
+        if (lo > hi) return fail(FLY_E_ARG, "fly_set_randomization: %s range is not ordered (%g > %g)", names[j], (double)lo, (double)hi);
+    }
+    if (!env_params) return fail(FLY_E_ARG, "fly_set_randomization: env_params is null");
+    if (reinterpret_cast<uintptr_t>(env_params) & 15) return fail(FLY_E_ARG, "fly_set_randomization: env_params is not 16-byte aligned");
+    DrSlot slot;
+    slot.table = env_params;
+    slot.r = *r;
+    // synchronous: the slot holds the new table and ranges before the registration draw and any later launch read them
+    hipError_t e = hipMemcpy(reinterpret_cast<char*>(h->dev) + DR_SLOT, &slot, sizeof(slot), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return hip_fail(e, "fly_set_randomization");
+    e = flyhip_launch_dr_register(h->dev, h->host.num_envs, stream);
+    if (e != hipSuccess) return hip_fail(e, "fly_set_randomization launch");
+    h->dr_table = env_params;
     return FLY_OK;
 }
 

@@ -28,6 +28,7 @@
 #include "flyhip.h"
 #include "mlp_layout.h"
 #include "obs_norm.h"
+#include "domain_rand.h"
 
 namespace {
 
@@ -54,7 +55,8 @@ static_assert(MLP_IN == OBS_NORM_COLS && OBS_NORM_TABLE <= THREADS, "one table e
 
 // B3: the policy body on the bf16 matrix pipe (three-term splits; PF then points at the term planes)
 // NORM: the policy input is normalised under the table registered with the handle (fly_set_obs_norm, read through `c`)
-template <bool B3, bool NORM = false>
+// DR: the env step runs on each env's randomised constants and redraws them at its resets (fly_set_randomization, through `c`)
+template <bool B3, bool NORM = false, bool DR = false>
 __global__ __launch_bounds__(THREADS, B3 ? 1 : 2) void rollout_step_kernel(
     const FlyConfig* __restrict__ c, FlyBuffers b, const float* __restrict__ P, const void* __restrict__ PF,
     const float* __restrict__ x, long n, const float* __restrict__ eps, const float* __restrict__ var, int var_steps,
@@ -68,7 +70,7 @@ __global__ __launch_bounds__(THREADS, B3 ? 1 : 2) void rollout_step_kernel(
     var_steps -= var_base ? *var_base : 0;                  // pending decays: frozen row index minus what is already applied
     constexpr int PH_ALL = PH_SCALE | PH_RESET | PH_INTEGRATE | PH_OBS | PH_PROGRESS | PH_REWARD;
     FlyRegs st;
-    fly_load<PH_ALL>(st, c, b, blockIdx.x);                 // the env state's HBM round trip hides under the forward
+    fly_load<PH_ALL, DR>(st, c, b, blockIdx.x);             // the env state's HBM round trip hides under the forward
     if (NORM) __syncthreads();                              // publishes the table
     if (B3)
         forward_body_b3<false, false, NORM>(lds, blockIdx.x, 1L << 40, P, static_cast<const u16*>(PF), x, n, nullptr, v_out, nullptr,
@@ -81,7 +83,7 @@ __global__ __launch_bounds__(THREADS, B3 ? 1 : 2) void rollout_step_kernel(
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_s_waitcnt(0);          // this thread's action stores are acknowledged by L2
     __syncthreads();
-    fly_body<PH_ALL>(c, act, b, lds, blockIdx.x, st);
+    fly_body<PH_ALL, DR>(c, act, b, lds, blockIdx.x, st);
 }
 
 // Pose record (fly_set_pose_record): env 0's pose after step t -- root position, quaternion xyzw, the 18 joint angles in DoF
@@ -114,7 +116,8 @@ __device__ __forceinline__ void store_pose(float* __restrict__ poses, int t, con
 // envs: the step body plus the carried env state want ~300 registers and spill at 256), 2 beyond that.
 // REC: store env 0's pose of every step to poses [T][FLY_POSE_FLOATS] (store_pose); the other instantiations ignore `poses`.
 // NORM: the policy input of every step is normalised (rollout_step_kernel's NORM); the observation ring stays raw.
-template <bool B3, int WPS, bool REC, bool NORM = false>
+// DR: rollout_step_kernel's DR; the env's multipliers and draw count ride in FlyRegs from step to step (read once, stored at draws).
+template <bool B3, int WPS, bool REC, bool NORM = false, bool DR = false>
 __global__ __launch_bounds__(THREADS, WPS) void rollout_all_kernel(
     const FlyConfig* __restrict__ c, FlyBuffers b, const float* __restrict__ P, const void* __restrict__ PF,
     float* __restrict__ obs_ring, long n, const float* __restrict__ eps_all, const float* __restrict__ var, float var_decay,
@@ -139,7 +142,7 @@ __global__ __launch_bounds__(THREADS, WPS) void rollout_all_kernel(
     // flush can run until it has finished, so `var` is exactly the variance of row 0
     if (threadIdx.x < MLP_NACT) varcur[threadIdx.x] = var[threadIdx.x];
     FlyRegs st;
-    fly_load<PH_ALL>(st, c, b, blockIdx.x);
+    fly_load<PH_ALL, DR>(st, c, b, blockIdx.x);
     __syncthreads();
     const bool whole = (long)(blockIdx.x + 1) * BM <= n;         // a ragged last tile keeps the HBM hand-offs (its LDS rows are partly stale)
     for (int t = 0; t < T; ++t) {
@@ -164,7 +167,7 @@ __global__ __launch_bounds__(THREADS, WPS) void rollout_all_kernel(
         }
         __syncthreads();
         FlyRegs nx;
-        fly_body<PH_ALL>(c, act, b, lds, blockIdx.x, st, &nx, in_lds ? acts : nullptr);
+        fly_body<PH_ALL, DR>(c, act, b, lds, blockIdx.x, st, &nx, in_lds ? acts : nullptr);
         if (REC && blockIdx.x == 0) store_pose(poses, t, nx);
         st = nx;
         if (threadIdx.x < MLP_NACT && var_decay > 0.0f) varcur[threadIdx.x] = fmaxf(var_min, varcur[threadIdx.x] - var_decay);
@@ -184,7 +187,8 @@ __global__ __launch_bounds__(THREADS, WPS) void rollout_all_kernel(
 // REC: the pose record of rollout_all_kernel (store_pose, workgroup 0's first tile), poses [T][FLY_POSE_FLOATS] in `aux`.
 // NORM: the observation block is normalised before its conversion (policy_tile_fs); the table sits behind the FR_LDS_BYTES of
 // the image (the launch asks for NORM_LDS_FLOATS more).
-template <bool STAMP, bool MULTI, bool REC, bool NORM = false>
+// DR: rollout_all_kernel's DR (each tile's rows are read by its fly_load, then carried in FlyRegs).
+template <bool STAMP, bool MULTI, bool REC, bool NORM = false, bool DR = false>
 __global__ __launch_bounds__(THREADS, 1) void rollout_all_fs_kernel(
     const FlyConfig* __restrict__ c, FlyBuffers b, const float* __restrict__ P, const u16* __restrict__ PB,
     float* __restrict__ obs_ring, long n, const float* __restrict__ eps_all, const float* __restrict__ var, float var_decay,
@@ -194,7 +198,7 @@ __global__ __launch_bounds__(THREADS, 1) void rollout_all_fs_kernel(
 {
     // aux: the stamps (STAMP) or the pose record (REC) -- one slot, so that the kernel arguments, and with them the offsets of the
     // implicit ones (gridDim), stay those of the kernel without recording
-    static_assert(!(STAMP && REC) && !(STAMP && NORM), "the stamped diagnostic form neither records nor normalises");
+    static_assert(!(STAMP && REC) && !(STAMP && NORM) && !(STAMP && DR), "the stamped diagnostic form neither records, normalises nor randomises");
     unsigned long long* const stamps = static_cast<unsigned long long*>(aux);
     float* const poses = static_cast<float*>(aux);
     extern __shared__ __attribute__((aligned(16))) u16 fr_lds[];
@@ -214,7 +218,7 @@ __global__ __launch_bounds__(THREADS, 1) void rollout_all_fs_kernel(
         if (threadIdx.x < 32) L.varcur[threadIdx.x] = threadIdx.x < MLP_NACT ? var[threadIdx.x] : 1.0f;   // the variance of row 0 (see rollout_all_kernel)
         b.reset = reset0; b.progress = progress0;
         FlyRegs st;
-        fly_load<PH_ALL>(st, c, b, (int)tile);
+        fly_load<PH_ALL, DR>(st, c, b, (int)tile);
         WeightHeadT<2> w1;
         policy_tile_fs_head(w1, PB);
         __syncthreads();
@@ -231,7 +235,7 @@ __global__ __launch_bounds__(THREADS, 1) void rollout_all_fs_kernel(
             policy_tile_fs_head(w1, PB);     // the NEXT step's first weights: their round trip hides under the physics (A/B: requested
                                              // after the env step; not kept)
             FlyRegs nx;
-            fly_body<PH_ALL>(c, act, b, L.obs, (int)tile, st, &nx, L.acts);
+            fly_body<PH_ALL, DR>(c, act, b, L.obs, (int)tile, st, &nx, L.acts);
             if (REC && tile == 0) store_pose(poses, t, nx);
             st = nx;
             if (threadIdx.x < MLP_NACT && var_decay > 0.0f) L.varcur[threadIdx.x] = fmaxf(var_min, L.varcur[threadIdx.x] - var_decay);
@@ -245,32 +249,44 @@ __global__ __launch_bounds__(THREADS, 1) void rollout_all_fs_kernel(
 
 }  // namespace
 
-// the normalising instantiations of rollout_all_fs_kernel (the table is read through dcfg: the argument list is the plain one's)
-template <bool MULTI, bool REC>
-static hipError_t launch_rollout_all_fs_norm(dim3 grid, hipStream_t stream, const FlyConfig* dcfg, const FlyBuffers* b, const float* P,
-                                             const uint16_t* PB, float* obs_ring, long n, const float* eps_all, const float* var,
-                                             float var_decay, float var_min, float* act_all, float* logp_all, float* v_ring,
-                                             float* reward_all, int T, int64_t* reset_rows, int64_t* progress_rows, void* aux)
+// the normalising and / or randomising instantiations of rollout_all_fs_kernel (the table and the randomisation slot are read
+// through dcfg: the argument list is the plain one's)
+#define RAFS_OPT_PARAMS dim3 grid, hipStream_t stream, const FlyConfig* dcfg, const FlyBuffers* b, const float* P, const uint16_t* PB,      \
+                        float* obs_ring, long n, const float* eps_all, const float* var, float var_decay, float var_min, float* act_all,  \
+                        float* logp_all, float* v_ring, float* reward_all, int T, int64_t* reset_rows, int64_t* progress_rows, void* aux
+#define RAFS_OPT_ARGS grid, stream, dcfg, b, P, PB, obs_ring, n, eps_all, var, var_decay, var_min, act_all, logp_all, v_ring, reward_all, T, \
+                      reset_rows, progress_rows, aux
+template <bool MULTI, bool REC, bool NORM, bool DR>
+static hipError_t launch_rollout_all_fs_opt(RAFS_OPT_PARAMS)
 {
-    const int bytes = FR_LDS_BYTES + NORM_LDS_FLOATS * 4;
+    const int bytes = FR_LDS_BYTES + (NORM ? NORM_LDS_FLOATS * 4 : 0);
     static_assert(FR_LDS_BYTES % 4 == 0, "the table follows the image");
-    hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(rollout_all_fs_kernel<false, MULTI, REC, true>),
+    hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(rollout_all_fs_kernel<false, MULTI, REC, NORM, DR>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     if (ea != hipSuccess) return ea;
-    hipLaunchKernelGGL((rollout_all_fs_kernel<false, MULTI, REC, true>), grid, dim3(THREADS), bytes, stream, dcfg, *b, P, PB, obs_ring,
+    hipLaunchKernelGGL((rollout_all_fs_kernel<false, MULTI, REC, NORM, DR>), grid, dim3(THREADS), bytes, stream, dcfg, *b, P, PB, obs_ring,
                        n, eps_all, var, var_decay, var_min, act_all, logp_all, v_ring, reward_all, T, reset_rows, progress_rows, aux);
     return hipGetLastError();
 }
+template <bool NORM, bool DR>
+static hipError_t launch_rollout_all_fs_opt(bool multi, bool rec, RAFS_OPT_PARAMS)
+{
+    return multi ? (rec ? launch_rollout_all_fs_opt<true, true, NORM, DR>(RAFS_OPT_ARGS) : launch_rollout_all_fs_opt<true, false, NORM, DR>(RAFS_OPT_ARGS))
+                 : (rec ? launch_rollout_all_fs_opt<false, true, NORM, DR>(RAFS_OPT_ARGS) : launch_rollout_all_fs_opt<false, false, NORM, DR>(RAFS_OPT_ARGS));
+}
+#undef RAFS_OPT_PARAMS
+#undef RAFS_OPT_ARGS
 
 // poses (optional, device [T][FLY_POSE_FLOATS]): launch the REC instantiation of whichever kernel the shape selects -- recording
 // never changes the launch form.  The stamped diagnostic instantiation does not record.  norm: the NORM instantiation of the same
-// kernel (the table registered in dcfg's slot, fly_set_obs_norm); not with stamps.
+// kernel (the table registered in dcfg's slot, fly_set_obs_norm); dr: its DR instantiation (fly_set_randomization); neither with
+// stamps.
 extern "C" hipError_t flyhip_launch_rollout_all(const FlyConfig* dcfg, const FlyBuffers* b, const float* P, const float* PF,
                                                 float* obs_ring, int64_t n, const float* eps_all, const float* var,
                                                 float var_decay, float var_min, float* act_all, float* logp_all, float* v_ring,
                                                 float* reward_all, int T, const int* rows_applied, const uint16_t* PB,
                                                 int64_t* reset_rows, int64_t* progress_rows, void* stream,
-                                                unsigned long long* stamps, float* poses, int norm)
+                                                unsigned long long* stamps, float* poses, int norm, int dr)
 {
     const dim3 grid((unsigned)((n + BM - 1) / BM));
     int cus = 256;
@@ -279,16 +295,16 @@ extern "C" hipError_t flyhip_launch_rollout_all(const FlyConfig* dcfg, const Fly
     const dim3 grid_fs((unsigned)((int)grid.x <= cus ? (int)grid.x : cus));   // the fused-style kernel walks its tiles itself
     const char* fs_env = getenv("FLY_ROLLOUT_FS");               // read per launch: the tests flip it inside one process
     const bool fs_off = fs_env != nullptr && fs_env[0] == '0';
-    if (stamps && (poses || norm)) return hipErrorInvalidValue;
+    if (stamps && (poses || norm || dr)) return hipErrorInvalidValue;
     const bool rec = poses != nullptr;
     if (PB && n % BM == 0 && !fs_off) {       // the policy body in the fused step's style (A/B: FLY_ROLLOUT_FS=0); persistent over tiles
         const bool multi = (int)grid.x > cus;
-        if (norm) {
-#define RAFS_NORM(M_, R_) launch_rollout_all_fs_norm<M_, R_>(grid_fs, (hipStream_t)stream, dcfg, b, P, PB, obs_ring, (long)n, eps_all, var, \
-                                                             var_decay, var_min, act_all, logp_all, v_ring, reward_all, T, reset_rows,    \
-                                                             progress_rows, poses)
-            return multi ? (rec ? RAFS_NORM(true, true) : RAFS_NORM(true, false)) : (rec ? RAFS_NORM(false, true) : RAFS_NORM(false, false));
-#undef RAFS_NORM
+        if (norm || dr) {
+#define RAFS_OPT(N_, D_) launch_rollout_all_fs_opt<N_, D_>(multi, rec, grid_fs, (hipStream_t)stream, dcfg, b, P, PB, obs_ring, (long)n, eps_all, \
+                                                           var, var_decay, var_min, act_all, logp_all, v_ring, reward_all, T, reset_rows,    \
+                                                           progress_rows, poses)
+            return norm && dr ? RAFS_OPT(true, true) : norm ? RAFS_OPT(true, false) : RAFS_OPT(false, true);
+#undef RAFS_OPT
         }
         const int si = (stamps ? 1 : 0) + (multi ? 2 : 0) + (rec ? 4 : 0);
         const void* fn = si == 0 ? reinterpret_cast<const void*>(rollout_all_fs_kernel<false, false, false>)
@@ -312,28 +328,26 @@ extern "C" hipError_t flyhip_launch_rollout_all(const FlyConfig* dcfg, const Fly
         return hipGetLastError();
     }
     if (stamps) return hipErrorInvalidValue;        // only the fused-style kernel has a stamped instantiation
+#define RA_K(B3_, WPS_, PF_, R_, N_, D_)                                                                                          \
+    hipLaunchKernelGGL((rollout_all_kernel<B3_, WPS_, R_, N_, D_>), grid, dim3(THREADS), 0, (hipStream_t)stream, dcfg, *b, P,          \
+                       (const void*)PF_, obs_ring, (long)n, eps_all, var, var_decay, var_min, act_all, logp_all, v_ring, reward_all, T, \
+                       rows_applied, reset_rows, progress_rows, poses)
+#define RA_LAUNCH_D(B3_, WPS_, PF_, D_)                                                                                            \
+    do {                                                                                                                           \
+        if (norm && rec) RA_K(B3_, WPS_, PF_, true, true, D_);                                                                     \
+        else if (norm) RA_K(B3_, WPS_, PF_, false, true, D_);                                                                      \
+        else if (rec) RA_K(B3_, WPS_, PF_, true, false, D_);                                                                       \
+        else RA_K(B3_, WPS_, PF_, false, false, D_);                                                                               \
+    } while (0)
 #define RA_LAUNCH(B3_, WPS_, PF_)                                                                                                  \
     do {                                                                                                                           \
-        if (norm && rec)                                                                                                           \
-            hipLaunchKernelGGL((rollout_all_kernel<B3_, WPS_, true, true>), grid, dim3(THREADS), 0, (hipStream_t)stream, dcfg, *b, \
-                               P, (const void*)PF_, obs_ring, (long)n, eps_all, var, var_decay, var_min, act_all, logp_all, v_ring, \
-                               reward_all, T, rows_applied, reset_rows, progress_rows, poses);                                      \
-        else if (norm)                                                                                                             \
-            hipLaunchKernelGGL((rollout_all_kernel<B3_, WPS_, false, true>), grid, dim3(THREADS), 0, (hipStream_t)stream, dcfg, *b,\
-                               P, (const void*)PF_, obs_ring, (long)n, eps_all, var, var_decay, var_min, act_all, logp_all, v_ring, \
-                               reward_all, T, rows_applied, reset_rows, progress_rows, poses);                                      \
-        else if (rec)                                                                                                              \
-            hipLaunchKernelGGL((rollout_all_kernel<B3_, WPS_, true>), grid, dim3(THREADS), 0, (hipStream_t)stream, dcfg, *b, P,     \
-                               (const void*)PF_, obs_ring, (long)n, eps_all, var, var_decay, var_min, act_all, logp_all, v_ring,    \
-                               reward_all, T, rows_applied, reset_rows, progress_rows, poses);                                      \
-        else                                                                                                                       \
-            hipLaunchKernelGGL((rollout_all_kernel<B3_, WPS_, false>), grid, dim3(THREADS), 0, (hipStream_t)stream, dcfg, *b, P,    \
-                               (const void*)PF_, obs_ring, (long)n, eps_all, var, var_decay, var_min, act_all, logp_all, v_ring,    \
-                               reward_all, T, rows_applied, reset_rows, progress_rows, poses);                                      \
+        if (dr) RA_LAUNCH_D(B3_, WPS_, PF_, true); else RA_LAUNCH_D(B3_, WPS_, PF_, false);                                        \
     } while (0)
     if (PB) { if (one_per_cu) RA_LAUNCH(true, 1, PB); else RA_LAUNCH(true, 1, PB); }      // the bf16x3 body needs one wave per SIMD anyway
     else { if (one_per_cu) RA_LAUNCH(false, 1, PF); else RA_LAUNCH(false, 2, PF); }
 #undef RA_LAUNCH
+#undef RA_LAUNCH_D
+#undef RA_K
     return hipGetLastError();
 }
 
@@ -482,21 +496,25 @@ extern "C" int flyhip_debug_mlp_fwd_bwd_stamped(const float* P, const float* PF,
 extern "C" hipError_t flyhip_launch_rollout_step(const FlyConfig* dcfg, const FlyBuffers* b, const float* P, const float* PF,
                                                  const float* x, int64_t n, const float* eps, const float* var, int var_steps,
                                                  float var_decay, float var_min, float* act, float* logp, float* v_out,
-                                                 const uint16_t* PB, const int* var_base, void* stream, int norm)
+                                                 const uint16_t* PB, const int* var_base, void* stream, int norm, int dr)
 {
     const dim3 grid((unsigned)((n + BM - 1) / BM));
-    if (norm && PB)
-        hipLaunchKernelGGL((rollout_step_kernel<true, true>), grid, dim3(THREADS), 0, (hipStream_t)stream, dcfg, *b, P, (const void*)PB,
-                           x, (long)n, eps, var, var_steps, var_decay, var_min, act, logp, v_out, var_base);
-    else if (norm)
-        hipLaunchKernelGGL((rollout_step_kernel<false, true>), grid, dim3(THREADS), 0, (hipStream_t)stream, dcfg, *b, P, (const void*)PF,
-                           x, (long)n, eps, var, var_steps, var_decay, var_min, act, logp, v_out, var_base);
-    else if (PB)
-        hipLaunchKernelGGL(rollout_step_kernel<true>, grid, dim3(THREADS), 0, (hipStream_t)stream, dcfg, *b, P, (const void*)PB,
-                           x, (long)n, eps, var, var_steps, var_decay, var_min, act, logp, v_out, var_base);
-    else
-        hipLaunchKernelGGL(rollout_step_kernel<false>, grid, dim3(THREADS), 0, (hipStream_t)stream, dcfg, *b, P, (const void*)PF,
-                           x, (long)n, eps, var, var_steps, var_decay, var_min, act, logp, v_out, var_base);
+#define RS_K(B3_, N_, D_)                                                                                                           \
+    hipLaunchKernelGGL((rollout_step_kernel<B3_, N_, D_>), grid, dim3(THREADS), 0, (hipStream_t)stream, dcfg, *b, P,                \
+                       B3_ ? (const void*)PB : (const void*)PF, x, (long)n, eps, var, var_steps, var_decay, var_min, act, logp, v_out, \
+                       var_base)
+    if (dr) {
+        if (norm && PB) RS_K(true, true, true);
+        else if (norm) RS_K(false, true, true);
+        else if (PB) RS_K(true, false, true);
+        else RS_K(false, false, true);
+    } else {
+        if (norm && PB) RS_K(true, true, false);
+        else if (norm) RS_K(false, true, false);
+        else if (PB) RS_K(true, false, false);
+        else RS_K(false, false, false);
+    }
+#undef RS_K
     return hipGetLastError();
 }
 

@@ -6,17 +6,64 @@ attributes (`num_obs`, `num_act`, `obs_buf`, `reward_buf`, `reset_buf`, `progres
 (`step`, `reset`, `get_obs`, `get_reward`, `simulate`, `render`, `generate_video`, `exit`).  What
 was a chain of torch ops plus Isaac Gym calls per step is ONE kernel launch through the C ABI
 (`fly_step`, include/flyhip.h); the unfused methods launch the matching single-phase kernels.
-With `args.record`, rank 0 records env 0 (record.py).
+With `args.record`, rank 0 records env 0 (record.py).  With `args.randomize`, every env runs FlyDyn on its own
+multiplied constants, redrawn at each of its resets (`set_randomization`).
 
 No Isaac Gym, no PhysX, no CPU path: the rigid-body model behind `simulate()` is the
 build-defined FlyDyn because the reference's physics is a closed binary.
 """
 import ctypes as C
+import math
 
 import torch
 
 from . import _lib
 from .params import NUM_CONTACT, NUM_DOF, NUM_OBS, ROOT_DIM, default_params
+
+# per-env physics domain randomisation (include/flyhip.h, fly_set_randomization): multipliers of these FlyConfig values, in
+# this order; `mass` scales the inertia too
+DR_NAMES = ("kp", "kd", "effort", "mass", "mu", "gravity")
+# trainer.py's starting ranges (--dr_*): not tuned
+DR_DEFAULT_RANGES = {"kp": (0.8, 1.2), "kd": (0.8, 1.2), "effort": (1.0, 1.0), "mass": (0.8, 1.2), "mu": (0.5, 1.5),
+                     "gravity": (1.0, 1.0)}
+DR_RANK_STRIDE = 0x9E3779B9         # rank r of a data-parallel run draws with seed + r * this (mod 2^32)
+
+
+def dr_bounds(ranges):
+    """{name: (lo, hi)} -> (lo[6], hi[6]) as fp32, a missing name = (1, 1).  The ABI's rules, checked here first so that bad
+    input fails before any GPU call: finite bounds, lo > 0, lo <= hi (after rounding to fp32)."""
+    unknown = set(ranges) - set(DR_NAMES)
+    if unknown:
+        raise ValueError("unknown randomisation parameter(s) %s; expected some of %s" % (sorted(unknown), list(DR_NAMES)))
+    lo, hi = [], []
+    for name in DR_NAMES:
+        pair = ranges.get(name, (1.0, 1.0))
+        if len(pair) != 2:
+            raise ValueError("randomisation range of %s must be (lo, hi), got %r" % (name, pair))
+        a, b = (C.c_float(float(v)).value for v in pair)
+        if not (math.isfinite(a) and math.isfinite(b)):
+            raise ValueError("randomisation range of %s is not finite: %r" % (name, pair))
+        if not a > 0.0:
+            raise ValueError("randomisation lower bound of %s must be > 0, got %r" % (name, pair[0]))
+        if a > b:
+            raise ValueError("randomisation range of %s is not ordered: %r > %r" % (name, pair[0], pair[1]))
+        lo.append(a)
+        hi.append(b)
+    return lo, hi
+
+
+def dr_args(args):
+    """(ranges, seed) of `args.randomize`: the --dr_* ranges (defaults DR_DEFAULT_RANGES), and --dr_seed (default --seed)
+    offset by the rank, so that the ranks of a data-parallel run draw different constants."""
+    ranges = {}
+    for name in DR_NAMES:
+        v = getattr(args, "dr_" + name, None)
+        ranges[name] = tuple(v) if v is not None else DR_DEFAULT_RANGES[name]
+    seed = getattr(args, "dr_seed", None)
+    if seed is None:
+        seed = getattr(args, "seed", 0) or 0
+    rank = int(getattr(args, "rank", 0) or 0)
+    return ranges, (int(seed) + DR_RANK_STRIDE * rank) % (1 << 32)
 
 
 class Fly:
@@ -86,6 +133,15 @@ class Fly:
         self.finished_count = torch.zeros(n, **f32)
         self._bufs = _lib.FlyBuffers()
         self._refresh_pointers()
+        # per-env physics domain randomisation (opt-in): the [N, FLY_DR_ROW] table the kernels read and redraw; kept once made,
+        # so turning randomisation off and on again continues each env's draw count
+        self._dr_table = None
+        self._dr_on = False
+        # bumped whenever the kernels a launch selects change (randomisation on / off): captured graphs hold the old ones
+        self.launch_form = 0
+        if getattr(args, "randomize", False):
+            ranges, seed = dr_args(args)
+            self.set_randomization(ranges, seed)
         # recording (fly.py:592-610): env 0, rank 0 only (record.py)
         self.recorder = None
         if getattr(args, "record", False) and int(getattr(args, "rank", 0) or 0) == 0:
@@ -131,6 +187,41 @@ class Fly:
         return actions if actions.is_contiguous() else actions.contiguous()
 
     # ------------------------------------------------------------------------------------------
+    def set_randomization(self, ranges, seed=0):
+        """Per-env physics domain randomisation.  `ranges`: {name: (lo, hi)} over DR_NAMES, multipliers of the config's kp, kd,
+        effort, mass (and inertia), mu and gravity; a missing name is (1, 1).  Turning it on draws every env's multipliers once;
+        every reset the kernels perform then draws that env's next set.  `None` turns it off: the plain kernels run again and
+        the table is left as it is."""
+        if ranges is None:
+            _lib.check(self._lib.fly_set_randomization(self._handle, None, None, _lib.stream_ptr()), "fly_set_randomization")
+            self._dr_on = False
+            self.launch_form += 1
+            return
+        lo, hi = dr_bounds(ranges)
+        if self._dr_table is None:
+            self._dr_table = torch.zeros((self.args.num_envs, _lib.DR_ROW), dtype=torch.float32, device=self.device)
+        r = _lib.FlyRandomization()
+        r.lo[:], r.hi[:] = lo, hi
+        r.seed = int(seed) % (1 << 32)
+        _lib.check(self._lib.fly_set_randomization(self._handle, C.byref(r), C.c_void_p(self._dr_table.data_ptr()),
+                                                   _lib.stream_ptr()), "fly_set_randomization")
+        self._dr_on = True
+        self.launch_form += 1
+
+    @property
+    def randomized(self):
+        return self._dr_on
+
+    @property
+    def env_params(self):
+        """[N, 6] float32 view of each env's current multipliers (DR_NAMES order), or None when randomisation is off."""
+        return self._dr_table[:, :_lib.DR_PARAMS] if self._dr_on else None
+
+    @property
+    def env_param_draws(self):
+        """[N] int32 view of each env's draw count (None if randomisation was never on)."""
+        return None if self._dr_table is None else self._dr_table[:, _lib.DR_PARAMS].view(torch.int32)
+
     def step(self, actions):
         """fly.py:624-681 in one launch."""
         a = self._check_actions(actions)

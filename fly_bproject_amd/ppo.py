@@ -162,6 +162,7 @@ class PPO:
         self.persistent_rollout = bool(want) and T <= 4096 and not bool(getattr(args, "graph", False))
         self._reset_rows = self._progress_rows = None
         self._graphs = {}
+        self._graphs_form = getattr(self.env, "launch_form", 0)     # the env's kernel selection the captured graphs hold
         self._fwd_args = None
         self._score_acc = torch.zeros((), device=dev)
         # The reference prints its score line from a host read of device values (ppo.py:257-260).  A blocking read in the middle
@@ -795,6 +796,9 @@ class PPO:
         end = self.env.end
         if self._fwd_args is None or self._args_infer_gemm != self.policy.gemm_infer:
             self._prepare_step_args()                               # (re)built when the inference arithmetic changes
+        if self._graphs_form != getattr(self.env, "launch_form", 0):
+            self._graphs = {}                                       # randomisation turned on / off: captured kernels are stale
+            self._graphs_form = self.env.launch_form
         rec = self.env.recorder
         step_s = self.env.render_count                              # the env step this call runs (record.py)
         if rec is not None:

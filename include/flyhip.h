@@ -57,6 +57,8 @@ extern "C" {
 #define FLY_OBS_NORM_TABLE 147   /* observation normalisation table: mean[73] | rstd[73] | clip (f32) */
 #define FLY_OBS_NORM_SET 147     /* one set of statistics or moments: count | mean[73] | var or M2[73] (f64) */
 #define FLY_OBS_NORM_SETS 256    /* moment sets ppo_obs_norm_pass writes (one per workgroup) */
+#define FLY_DR_PARAMS 6   /* kp, kd, effort, mass (+ inertia), mu, gravity: multipliers of the FlyConfig values */
+#define FLY_DR_ROW 8      /* per-env row of the randomisation table, f32: m[6] | draw count (int32 bits) | 0 */
 
 #define FLY_OK 0
 #define FLY_E_ARG (-1)      /* bad argument (null pointer, bad size, misalignment) */
@@ -207,6 +209,30 @@ int ppo_obs_norm_pass(const float* ring, int64_t rows, int64_t count_from, const
                       void* stream);
 int ppo_obs_norm_merge(double* stats, float* table, const double* sets, int64_t k, float clip, void* stream);
 int fly_set_obs_norm(FlyHandle h, const float* table);
+
+/* Per-env physics domain randomisation (opt-in).  The reference has none: every env of a batch runs
+ * the one parameter set of the config.  With a table registered, env e runs FlyDyn on its own constants
+ *     kp * m0, kd * m1, effort * m2, mass * m3 and inertia[i] * m3, mu * m4, gravity * m5   (fp32, rounded once each)
+ * and everything else (reward, observations, reset pose, the other constants) stays the config's.
+ * A draw is a pure function of (seed, e, k, j), k = the env's draw count before it, all uint32 arithmetic wrapping:
+ *     lowbias32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ *     key = lowbias32(seed ^ lowbias32(e)); ctr = lowbias32(key + k)
+ *     u_j = float(lowbias32(ctr + 0x9E3779B9 * (j + 1)) >> 8) * 2^-24;  m_j = lo_j + (hi_j - lo_j) * u_j  (two fp32 roundings)
+ * Registration draws once for every env (from its current count), and every reset the kernels perform draws again:
+ * before the step's physics when resets come first (bigGrav), for the next step when they come after (reset_after_sim).
+ * fly_set_randomization: r = ranges and seed (host struct, copied), NULL = off.  env_params: caller-owned device table
+ *   [N][FLY_DR_ROW], 16-byte aligned, whose counts (column 6) the caller zeroes before the first registration; the
+ *   registration draw runs on `stream`.  While set, fly_step, fly_reset_masked, fly_integrate, ppo_rollout_step and
+ *   ppo_rollout_all launch the randomising instantiation of their kernel; off, the plain ones again, and the table is left
+ *   as it is.  FLY_E_ARG for non-finite bounds, lo <= 0, lo > hi, a null or misaligned table while r is set, and with the
+ *   stamped diagnostic rollout. */
+typedef struct FlyRandomization {
+    float lo[FLY_DR_PARAMS];
+    float hi[FLY_DR_PARAMS];
+    uint32_t seed;
+    int32_t reserved;
+} FlyRandomization;
+int fly_set_randomization(FlyHandle h, const FlyRandomization* r, float* env_params, void* stream);
 
 /* ppo.py:233 and :237 without the per-step host sync: *score_acc += mean(reward) * score_scale;
  * action_var[j] = max(var_min, action_var[j] - var_decay) (skipped when var_decay <= 0). */

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Does the loop learn?  Runs ITERS PPO iterations at N envs and prints, per iteration, the mean
 per-step reward of the rollout and the episode statistics (mean return / length of finished
-episodes).  Usage: python tools/train_curve.py [ITERS] [N] [backend] [variant] [gemm: f16x2 (default) | bf16x3 | f32] [norm]
-`norm` as the sixth argument turns on observation normalisation (--normalize_obs)."""
+episodes).  Usage: python tools/train_curve.py [ITERS] [N] [backend] [variant] [gemm: f16x2 (default) | bf16x3 | f32] [norm] [dr]
+`norm` after the fifth argument turns on observation normalisation (--normalize_obs), `dr` per-env physics domain randomisation
+with trainer.py's default ranges (--randomize)."""
 import contextlib
 import io
 import os
@@ -20,14 +21,15 @@ n = int(sys.argv[2]) if len(sys.argv) > 2 else 8192
 backend = sys.argv[3] if len(sys.argv) > 3 else "hip"
 variant = sys.argv[4] if len(sys.argv) > 4 else "bigGrav"
 gemm = sys.argv[5] if len(sys.argv) > 5 and sys.argv[5] != "-" else None
-norm = len(sys.argv) > 6 and sys.argv[6] == "norm"
+norm = "norm" in sys.argv[6:]
+dr = "dr" in sys.argv[6:]
 torch.manual_seed(0)
 with contextlib.redirect_stdout(io.StringIO()):
-    agent = PPO(make_args(n, update_backend=backend, variant=variant, normalize_obs=norm))
+    agent = PPO(make_args(n, update_backend=backend, variant=variant, normalize_obs=norm, randomize=dr))
     if gemm:
         agent.policy.gemm = gemm
-print("arithmetic: gemm=%s step_gemm=%s (%s) normalize_obs=%s" % (agent.policy.gemm, agent.policy.step_gemm, agent.policy.update_path(),
-                                                                  norm))
+print("arithmetic: gemm=%s step_gemm=%s (%s) normalize_obs=%s randomize=%s" % (agent.policy.gemm, agent.policy.step_gemm,
+                                                                               agent.policy.update_path(), norm, dr))
 t0 = time.perf_counter()
 for it in range(iters):
     with contextlib.redirect_stdout(io.StringIO()):

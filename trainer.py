@@ -9,6 +9,9 @@ Same flags (`--sim_device --compute_device_id --graphics_device_id --num_envs --
 `--normalize_obs` (running mean / std normalisation of the policy input, rl_games' normalize_input; off by default) with
 `--obs_clip` (the bound of a normalised input, default 5.0): the statistics are saved with the checkpoint as obs_rms.* and
 loaded with it; such a checkpoint needs `--normalize_obs` to load.
+`--randomize` (per-env physics domain randomisation, off by default): each env runs on its own multipliers of kp, kd, effort,
+mass (and inertia), mu and gravity, drawn from `--dr_<name> LO HI` at every reset of that env with seed `--dr_seed` (default
+`--seed`; rank r adds r * 0x9E3779B9).  A property of the env: nothing of it goes into the checkpoint.
 Recording (`--record True` or `--record_dir_name DIR`): rank 0 renders env 0 on the GPU every
 `--time_steps_per_recorded_frame` env steps to DIR/frame_%06d.png (fly_bproject_amd/record.py) and, when ffmpeg is on
 PATH, assembles DIR.mp4 at the end.  Unlike the reference, which records only with its viewer open, recording does not
@@ -62,6 +65,14 @@ def parse_args(argv=None):
                         help='normalise the policy input by running mean / std of the observations, clamped to +-obs_clip '
                              '(rl_games normalize_input; not in the reference; off by default)')
     parser.add_argument('--obs_clip', type=float, default=5.0, help='bound of a normalised observation (with --normalize_obs)')
+    parser.add_argument('--randomize', action='store_true',
+                        help='per-env physics domain randomisation, redrawn at every reset of the env (Isaac Gym actor-property '
+                             'randomisation; not in the reference; off by default)')
+    from fly_bproject_amd.fly import DR_DEFAULT_RANGES, DR_NAMES
+    for name in DR_NAMES:
+        parser.add_argument('--dr_' + name, type=float, nargs=2, default=list(DR_DEFAULT_RANGES[name]), metavar=('LO', 'HI'),
+                            help='range of the %s multiplier (with --randomize; mass scales the inertia too)' % name)
+    parser.add_argument('--dr_seed', type=int, default=None, help='seed of the randomisation draws (default: --seed)')
     args = parser.parse_args(argv)
     if args.save_path is not None:          # trainer.py:27-34
         args.save = True
