@@ -101,14 +101,17 @@ struct DhDlreluOps {
     H2Chain k[4];
     __device__ __forceinline__ DhDlreluOps(const f32x16& hi_, const f32x16& lo_, int col0_, u16* plane0_, int lane_, float qs_)
         : hi(hi_), lo(lo_), plane0(plane0_), col0(col0_), lane(lane_), r(lane_ & 31), qs(qs_), am(0.0f), negmask(0u) {}
-    // a packed pair of leading fp16 terms: x > 0 <=> bit 15 of (x - 1) as a 16-bit integer is clear (x = 0 wraps to 0xffff, negative
-    // values keep theirs; -0.0 would read as positive: LeakyReLU's output is -0.0 only for a pre-activation of -0.0)
+    // a packed pair of leading fp16 terms: the flag is set (the slope applies) exactly where df_dlrelu_op takes the slope for dA1,
+    // i.e. where the term is <= 0 as a 16-bit integer -- +0.0 and -0.0 included.  Both zeros occur for nonzero pre-activations: the
+    // leading term of h s_H2 flushes to +0.0 for 0 < z < 2^-25 / s_H2 and to -0.0 for 0 > z > -2^-25 / (0.01 s_H2) (LeakyReLU's
+    // slope makes the negative window 100x wider).  x <= 0 <=> bit 15 of the SATURATING x - 1 is set (one v_pk_add_i16 ... clamp:
+    // 0 -> -1, -0.0 = -32768 stays -32768; a wrapping subtraction would read -0.0 as 0x7fff, positive)
     __device__ __forceinline__ void fold(unsigned w, int kbit)
     {
-        typedef unsigned short dh_u16x2 __attribute__((ext_vector_type(2)));
-        dh_u16x2 x = __builtin_bit_cast(dh_u16x2, w);
-        const dh_u16x2 one = {1, 1};
-        x = x - one;
+        typedef short dh_s16x2 __attribute__((ext_vector_type(2)));
+        dh_s16x2 x = __builtin_bit_cast(dh_s16x2, w);
+        const dh_s16x2 one = {1, 1};
+        x = __builtin_elementwise_sub_sat(x, one);
         negmask |= ((__builtin_bit_cast(unsigned, x) >> 15) & 0x00010001u) << kbit;
     }
     __device__ __forceinline__ void chain_op(H2Chain& c, int g, int h, int i, const uint2& w)

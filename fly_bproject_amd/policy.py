@@ -105,6 +105,9 @@ PH_HALVES, PTH_HALVES = PB_HALVES * 2 // 3, PTB_HALVES * 2 // 3
 H2_SCALE_FLOATS, H2_INV, H2_W0 = 2386, 16, 8        # (csrc/mlp_adam.inc: [40, 41] and [64 ..) are mlp_adam_step's rescale bookkeeping)
 H2_SINCE, H2_WMAX, H2_WMAX_SLOTS = 40, 64, 1161
 H2_CLASSES = ("x", "h1", "h2", "h3", "dz4", "dz3", "dz2", "dz1")
+# where the step steers a class maximum of |scaled value| -- [2^e, 2^(e + 1)) -- and the floor under which a launch is refused
+# (csrc/fs_h2.inc: H2_TARGET_EXP_ACT / _GRAD, H2_CLASS_FLOOR; the tests derive their windows and bars from these)
+H2_TARGET_EXP_ACT, H2_TARGET_EXP_GRAD, H2_CLASS_FLOOR = 7, 2, 2.0 ** -8
 
 
 def split_f16x2(w, scale):

@@ -151,11 +151,12 @@ def test_h2_is_deterministic_and_grid_independent():
 
 def test_h2_scales_follow_the_data_and_the_planes_follow_the_weights():
     """After a launch every class's scale puts THAT launch's largest |value| into the class's window ([2^7, 2^8) for x / h1 .. h3,
-    [2^2, 2^3) for dz4 .. dz1: csrc/mlp_fused_h2.inc, h2_target_exp); the
+    [2^2, 2^3) for dz4 .. dz1: csrc/fs_h2.inc, h2_target_exp); the
     weight planes mlp_adam_step maintains equal a fresh split of the weights under the scales it published, whose headroom over the
     current max |w| is 8x .. 64x (16x .. 32x when the scale was set; max |w| counted as 2^-4 at least)."""
     import math
-    from fly_bproject_amd.policy import H2_INV, H2_W0, OFF_W1, OFF_W2, OFF_W3, OFF_W4, PACKED, split_f16x2
+    from fly_bproject_amd.policy import (H2_INV, H2_TARGET_EXP_ACT, H2_TARGET_EXP_GRAD, H2_W0, OFF_W1, OFF_W2, OFF_W3, OFF_W4, PACKED,
+                                         split_f16x2)
     n = 4099
     net, ref, pol, batch = _setup(n, 7, gemm="f16x2")
     x, action, old_logp, adv, target, var = batch
@@ -170,7 +171,7 @@ def test_h2_scales_follow_the_data_and_the_planes_follow_the_weights():
     c = _chain(pol, n)
     true_max = [float(x.abs().max()), *[float(c[k].abs().max()) for k in ("h1", "h2", "h3", "dz4", "dz3", "dz2", "dz1")]]
     for i, m in enumerate(true_max):
-        scaled, e = m * float(sc[i]), (7 if i < 4 else 2)
+        scaled, e = m * float(sc[i]), (H2_TARGET_EXP_ACT if i < 4 else H2_TARGET_EXP_GRAD)
         assert 2.0 ** e <= scaled * (1 + 1e-6) and scaled < 2.0 ** (e + 1) * (1 + 1e-6), (i, m, float(sc[i]), scaled)
         assert float(sc[i]) * float(sc[H2_INV + i]) == 1.0 and math.log2(float(sc[i])).is_integer()
     bounds = (OFF_W1, OFF_W2, OFF_W3, OFF_W4, PACKED)

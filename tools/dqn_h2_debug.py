@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Where does the fp16x2 DQN update's gradient differ from float64?  Per parameter tensor and, for layer 1, per 32-column tile of the
-hidden layer; with the lagged scales as calibrated and with single classes moved by 2^k (frozen).  dqn_h2_debug.py [parts] [n] [unambiguous]"""
+hidden layer; with the lagged scales as calibrated and with single classes moved by 2^k (frozen).  dqn_h2_debug.py [parts] [n] [kink]
+(kink: also the errors once the pairs next to LeakyReLU's kink that the kernel flipped are taken out, tests/test_dqn_h2_gpu.py)"""
 import os
 import sys
 
@@ -8,7 +9,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from tests.test_dqn import _bare_dqn  # noqa: E402
-from tests.test_dqn_h2_gpu import _batch, _grad64, _perturb_target, _restore, _state, _unambiguous, _views  # noqa: E402
+from tests.test_dqn_h2_gpu import _batch, _beyond, _grad64, _kink_reference, _perturb_target, _restore, _state, _views  # noqa: E402
 
 parts = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 8192
@@ -17,15 +18,19 @@ chunks = _batch(parts, n, 21)
 d = _bare_dqn(rows=n, fused=True, gemm="f16x2")
 _perturb_target(d)
 st = _state(d)
-if len(sys.argv) > 3:           # any third argument: rows with a hidden unit within 1e-5 of LeakyReLU's kink replaced (the tests' batches)
-    chunks, replaced = _unambiguous(d, chunks)
-    print("rows replaced:", replaced)
+kink = len(sys.argv) > 3
 want, loss64 = _grad64(d, chunks)
 
 
 def report(tag):
     errs = [float((g.double() - w).abs().max() / w.abs().max()) for g, w in zip(_views(d.packed.G), want)]
     print("%-34s %s" % (tag, " ".join("%.2e" % e for e in errs)), "refused", d.h2_overflows)
+    if kink:
+        sc = d.packed.h2_scales.cpu()                   # (the scales the NEXT launch uses: close enough for a diagnosis)
+        _restore(d, st)
+        w64, eff, n_amb, _, _ = _kink_reference(d, chunks, float(sc[1]), float(sc[2]))
+        e, flipped = _beyond(d.packed.G, w64, eff)
+        print("    kink pairs taken out (%d of %d ambiguous): %s" % (flipped, n_amb, " ".join("%.2e" % x for x in e)))
     g1, w1 = _views(d.packed.G)[0].double(), want[0]
     gb, wb = _views(d.packed.G)[1].double(), want[1]
     per = [(float((g1[32 * t:32 * t + 32] - w1[32 * t:32 * t + 32]).abs().max() / w1.abs().max()),

@@ -45,14 +45,16 @@ torch.cuda.synchronize()
 names = ["x", "h1", "h2", "h3", "dz4", "dz3", "dz2", "dz1"]
 print("updates: %d, traced fp16x2 steps: %d, updates with an overflow: %d" % (iters, len(trace), agent.policy.h2_overflows))
 print("step  " + "  ".join("%9s" % nm for nm in names) + "  ovf")
-worst = [0.0] * 8
+worst, up = [0.0] * 8, [0.0] * 8
 prev = None
 for i, row in enumerate(trace):
     if prev is not None:
         for c in range(8):
             if row[c] > 0 and prev[c] > 0:
                 worst[c] = max(worst[c], abs(math.log2(row[c] / prev[c])))
+                up[c] = max(up[c], math.log2(row[c] / prev[c]))       # a rise: what the headroom over the window must cover
     if i < 160 or row[8]:
         print("%4d  " % i + "  ".join("%9.3g" % v for v in row[:8]) + "  %d" % row[8])
     prev = row
 print("largest step-to-step move of a class maximum, in binades: " + "  ".join("%s %.1f" % (nm, w) for nm, w in zip(names, worst)))
+print("largest step-to-step rise of a class maximum, in binades:   " + "  ".join("%s %.1f" % (nm, w) for nm, w in zip(names, up)))
