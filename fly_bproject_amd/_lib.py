@@ -31,6 +31,9 @@ class FlyRandomization(C.Structure):
 POSE_FLOATS = 25        # FLY_POSE_FLOATS: root pos xyz | quat xyzw | 18 joint angles
 OBS_NORM_SET = 147      # FLY_OBS_NORM_SET / FLY_OBS_NORM_TABLE: count | mean[73] | var or M2[73] (f64); m[73] | r[73] | clip (f32)
 OBS_NORM_SETS = 256     # FLY_OBS_NORM_SETS: moment sets one ppo_obs_norm_pass writes
+VALUE_NORM_SET = 3      # FLY_VALUE_NORM_SET: count | mean | var or M2 (f64)
+VALUE_NORM_TABLE = 4    # FLY_VALUE_NORM_TABLE: m | s | r | 0 (f32)
+VALUE_NORM_SETS = 256   # FLY_VALUE_NORM_SETS: moment sets one ppo_td_gae_vnorm writes
 DR_PARAMS = 6           # FLY_DR_PARAMS: kp, kd, effort, mass (+ inertia), mu, gravity multipliers
 DR_ROW = 8              # FLY_DR_ROW: a randomisation table row, f32 m[6] | draw count (int32 bits) | 0
 ABI_VERSION = 13        # include/flyhip.h as this package binds it (fly_abi_version(): argument lists changed between versions)
@@ -56,6 +59,9 @@ SYMBOLS = {
     "ppo_adv_apply": [_P, _L, _P, _F, _F, _P],
     "ppo_obs_norm_pass": [_P, _L, _L, _P, _P, _P, _P],
     "ppo_obs_norm_merge": [_P, _P, _P, _L, _F, _P],
+    "ppo_td_gae_vnorm": [_P, _P, _P, _P, _P, _F, _F, _L, _L, _P, _P, _P, _I, _P],
+    "ppo_value_norm_merge": [_P, _P, _L, _P, _P, _P],
+    "ppo_value_norm_apply": [_P, _L, _P, _P, _P],
     "ppo_step_bookkeeping": [_P, _L, _P, _F, _P, _I, _F, _F, _P],
     "ppo_rollout_step": [_P, _P, _P, _P, _P, _P, _P, _I, _F, _F, _P, _P, _P, _P, _P, _P],
     "ppo_rollout_all": [_P, _P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],

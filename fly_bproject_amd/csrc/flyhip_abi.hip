@@ -122,6 +122,12 @@ extern "C" hipError_t flyhip_launch_obs_norm_pass(const float* ring, int64_t row
                                                   float* out, double* sets, void* stream);
 extern "C" hipError_t flyhip_launch_obs_norm_merge(double* stats, float* table, const double* sets, int64_t k, float clip,
                                                    void* stream);
+extern "C" hipError_t flyhip_launch_td_gae_vnorm(const float* reward, const float* v, const float* v_next, const float* done,
+                                                 const float* table, float gamma, float lambda, int64_t T, int64_t N,
+                                                 float* target_out, float* adv_out, double* sets, int mode, void* stream);
+extern "C" hipError_t flyhip_launch_value_norm_merge(const double* stats_in, const double* sets, int64_t k, double* stats_out,
+                                                     float* table_out, void* stream);
+extern "C" hipError_t flyhip_launch_value_norm_apply(const float* target, int64_t n, const float* table, float* out, void* stream);
 extern "C" hipError_t flyhip_launch_dr_register(const FlyConfig* dcfg, int n, void* stream);
 
 struct FlyEnv {
@@ -362,6 +368,45 @@ int ppo_obs_norm_merge(double* stats, float* table, const double* sets, int64_t 
     if (k <= 0 || !(clip > 0.0f)) return fail(FLY_E_ARG, "ppo_obs_norm_merge: bad argument");
     hipError_t e = flyhip_launch_obs_norm_merge(stats, table, sets, k, clip, stream);
     if (e != hipSuccess) return hip_fail(e, "ppo_obs_norm_merge launch");
+    return FLY_OK;
+}
+
+int ppo_td_gae_vnorm(const float* reward, const float* v, const float* v_next, const float* done, const float* table,
+                     float gamma, float lambda, int64_t T, int64_t N, float* target_out, float* adv_out, double* sets,
+                     int mode_flags, void* stream)
+{
+    if (!reward || !v || !v_next || !done || !table || !target_out || !adv_out || !sets)
+        return fail(FLY_E_ARG, "ppo_td_gae_vnorm: null pointer");
+    if (T <= 0 || N <= 0) return fail(FLY_E_ARG, "ppo_td_gae_vnorm: T and N must be > 0");
+    if (reinterpret_cast<uintptr_t>(sets) & 7) return fail(FLY_E_ARG, "ppo_td_gae_vnorm: sets is not 8-byte aligned");
+    if ((mode_flags & PPO_GAE_SCAN) && (mode_flags & PPO_GAE_MASK_RECURRENCE))
+        return fail(FLY_E_ARG, "ppo_td_gae_vnorm: PPO_GAE_SCAN does not implement the masked recurrence");
+    hipError_t e = flyhip_launch_td_gae_vnorm(reward, v, v_next, done, table, gamma, lambda, T, N, target_out, adv_out, sets,
+                                              mode_flags, stream);
+    if (e != hipSuccess) return hip_fail(e, "ppo_td_gae_vnorm launch");
+    return FLY_OK;
+}
+
+int ppo_value_norm_merge(const double* stats_in, const double* sets, int64_t k, double* stats_out, float* table_out, void* stream)
+{
+    if (!stats_in || !sets || !stats_out || !table_out) return fail(FLY_E_ARG, "ppo_value_norm_merge: null pointer");
+    if (k <= 0) return fail(FLY_E_ARG, "ppo_value_norm_merge: k must be > 0");
+    if ((reinterpret_cast<uintptr_t>(stats_in) | reinterpret_cast<uintptr_t>(sets) | reinterpret_cast<uintptr_t>(stats_out)) & 7)
+        return fail(FLY_E_ARG, "ppo_value_norm_merge: a float64 buffer is not 8-byte aligned");
+    if (stats_in < stats_out + FLY_VALUE_NORM_SET && stats_out < stats_in + FLY_VALUE_NORM_SET)
+        return fail(FLY_E_ARG, "ppo_value_norm_merge: stats_out must not overlap stats_in");
+    hipError_t e = flyhip_launch_value_norm_merge(stats_in, sets, k, stats_out, table_out, stream);
+    if (e != hipSuccess) return hip_fail(e, "ppo_value_norm_merge launch");
+    return FLY_OK;
+}
+
+int ppo_value_norm_apply(const float* target, int64_t n, const float* table, float* out, void* stream)
+{
+    if (!target || !table || !out) return fail(FLY_E_ARG, "ppo_value_norm_apply: null pointer");
+    if (n <= 0) return fail(FLY_E_ARG, "ppo_value_norm_apply: n must be > 0");
+    if (target < out + n && out < target + n) return fail(FLY_E_ARG, "ppo_value_norm_apply: out must not alias the targets");
+    hipError_t e = flyhip_launch_value_norm_apply(target, n, table, out, stream);
+    if (e != hipSuccess) return hip_fail(e, "ppo_value_norm_apply launch");
     return FLY_OK;
 }
 

@@ -186,8 +186,8 @@ def broadcast_parameters(module, src=0):
 
 def broadcast_policy(agent, src=0):
     """Replicate rank `src`'s policy: ONE broadcast of the packed parameter buffer, then rebuild
-    the fragment-ordered copies the kernels stream.  With observation normalisation, the running
-    statistics and the table the kernels read go along (a checkpoint loaded on rank 0 reaches
+    the fragment-ordered copies the kernels stream.  With observation or value normalisation, the
+    running statistics and the table the kernels read go along (a checkpoint loaded on rank 0 reaches
     every rank)."""
     if dist.is_initialized() and dist.get_world_size() > 1:
         dist.broadcast(agent.policy.P, src=src)
@@ -195,3 +195,6 @@ def broadcast_policy(agent, src=0):
         if getattr(agent, "normalize_obs", False):
             dist.broadcast(agent._obs_stats, src=src)
             dist.broadcast(agent._obs_table, src=src)
+        if getattr(agent, "normalize_value", False):
+            for buf in (agent._value_stats, agent._value_table, agent._value_stats_next, agent._value_table_next):
+                dist.broadcast(buf, src=src)

@@ -82,6 +82,29 @@ def split_obs_rms(state_dict, normalize_obs):
     return rms
 
 
+VALUE_RMS_KEYS = ("value_rms.mean", "value_rms.var", "value_rms.count")
+
+
+def split_value_rms(state_dict, normalize_value):
+    """split_obs_rms for the value statistics (value_rms.*): removed from the state dict, in place, and returned.  Statistics
+    without `normalize_value` are an error: the critic was trained on normalised targets, its outputs are not in reward units."""
+    rms = {k: state_dict.pop(k) for k in list(state_dict) if k.startswith("value_rms.")}
+    if rms and not normalize_value:
+        raise ValueError("this checkpoint was trained with value normalisation (it holds %s): run with --normalize_value"
+                         % ", ".join(sorted(rms)))
+    if rms and sorted(rms) != sorted(VALUE_RMS_KEYS):
+        raise ValueError("incomplete value statistics in the checkpoint: %s (want %s)" % (sorted(rms), list(VALUE_RMS_KEYS)))
+    return rms
+
+
+def value_norm_table(stats):
+    """The table the value-normalisation kernels read, from S_v = count | mean | var (float64): m = (float) mean,
+    s = (float) sqrt(var + 1e-5), r = (float) (1 / sqrt(var + 1e-5)), 0 -- each rounded once from float64 (what
+    ppo_value_norm_merge writes)."""
+    mean, sd = stats[1].double(), torch.sqrt(stats[2].double() + 1e-5)
+    return torch.stack((mean.float(), sd.float(), (1.0 / sd).float(), torch.zeros((), dtype=torch.float32, device=stats.device)))
+
+
 def obs_norm_table(stats, clip):
     """The table the kernels read, from S = count | mean[k] | var[k] (float64): m = (float) mean, r = (float) (1 / sqrt(var +
     1e-5)), clip -- each rounded once from float64 (what ppo_obs_norm_merge writes)."""
@@ -148,6 +171,9 @@ class PPO:
         self.obs_clip = float(getattr(args, "obs_clip", 5.0))
         if self.normalize_obs and not self.obs_clip > 0.0:
             raise ValueError("obs_clip must be > 0 (got %r)" % self.obs_clip)
+        # opt-in (`normalize_value`, rl_games' normalize_value): the critic regresses on TD targets kept at zero mean / unit
+        # variance by running statistics, and make_data maps its outputs back to reward units
+        self.normalize_value = bool(getattr(args, "normalize_value", False))
         self.use_graph = bool(getattr(args, "graph", False))
         # one launch per ROLLOUT (ppo_rollout_all): each workgroup loops over the T steps of its own 32 envs.  The device then
         # runs ahead of the host's step count inside a rollout, but everything `run()` reads per step is a ROW the launch wrote
@@ -188,11 +214,12 @@ class PPO:
         self.optim_step = 0
 
         self.net = Net(self.env.num_obs, self.env.num_act).to(dev)
-        loaded_rms = {}
+        loaded_rms, loaded_value_rms = {}, {}
         if getattr(self.args, "load", False):                       # ppo.py:147-149
             print("loaded from: ", str(self.args.load_path))
             sd = torch.load(self.args.load_path, map_location=dev, weights_only=True)
             loaded_rms = split_obs_rms(sd, self.normalize_obs)
+            loaded_value_rms = split_value_rms(sd, self.normalize_value)
             self.net.load_state_dict(sd)
         self._loaded = bool(getattr(self.args, "load", False))
         from .policy import PackedPolicy
@@ -216,6 +243,8 @@ class PPO:
         self._obs_norm_ring = None
         if self.normalize_obs:
             self._setup_obs_norm(loaded_rms)
+        if self.normalize_value:
+            self._setup_value_norm(loaded_value_rms)
         self._gen = torch.Generator(device=dev)
         self._gen.manual_seed(int(getattr(args, "seed", 0)) + 1000003 * int(getattr(args, "rank", 0)))
         self.world_size = int(getattr(args, "world_size", 1))
@@ -298,6 +327,79 @@ class PPO:
         _lib.check(self._lib.ppo_obs_norm_merge(p(self._obs_stats), p(self._obs_table), p(sets), C.c_int64(sets.shape[0]),
                                                 C.c_float(self.obs_clip), _lib.stream_ptr()), "ppo_obs_norm_merge")
 
+    # ------------------------------------------------------------------------------------------
+    # value normalisation (opt-in)
+    def _setup_value_norm(self, loaded_rms):
+        """The running statistics S_v of the TD targets (f64: count | mean | var, initially 0 | 0 | 1) and their table (f32:
+        m | s | r | 0): the COMMITTED pair, under which make_data denormalises the critic's outputs.  Beside it the scratch
+        pair make_data's merge writes (S_v with this rollout's targets folded in), the normalised copy of the targets and the
+        GAE pass's moment sets.  update() commits scratch -> committed by two device copies into these fixed addresses."""
+        dev = self.device
+        self._value_stats = torch.tensor([0.0, 0.0, 1.0], dtype=torch.float64, device=dev)
+        if loaded_rms:
+            for i, k in enumerate(("value_rms.count", "value_rms.mean", "value_rms.var")):
+                self._value_stats[i] = loaded_rms[k].to(dev, torch.float64).reshape(())
+        elif getattr(self.args, "load", False):
+            print("normalize_value: %s holds no value statistics (value_rms.*); starting from mean 0, var 1"
+                  % str(self.args.load_path))
+        self._value_table = value_norm_table(self._value_stats).contiguous()
+        self._value_stats_next = self._value_stats.clone()
+        self._value_table_next = self._value_table.clone()
+        self._target_norm = torch.zeros_like(self._target)
+        self._value_sets = torch.zeros((_lib.VALUE_NORM_SETS, _lib.VALUE_NORM_SET), dtype=torch.float64, device=dev)
+
+    @property
+    def value_mean(self):
+        """Running mean of the TD targets, reward units (f64 scalar, a copy), or None when value normalisation is off."""
+        return self._value_stats[1].clone() if self.normalize_value else None
+
+    @property
+    def value_var(self):
+        """Running population variance of the TD targets (f64 scalar, a copy), or None when value normalisation is off."""
+        return self._value_stats[2].clone() if self.normalize_value else None
+
+    @property
+    def value_count(self):
+        """Targets the running statistics are taken over (f64 scalar, a copy), or None when value normalisation is off."""
+        return self._value_stats[0].clone() if self.normalize_value else None
+
+    def denormalize_value(self, v):
+        """A critic output in reward units: v * s + m under the committed table in float32 (what make_data's GAE pass does);
+        `v` itself when value normalisation is off."""
+        if not self.normalize_value:
+            return v
+        return v * self._value_table[1] + self._value_table[0]
+
+    def _td_gae_vnorm(self, values, done_f, mode):
+        """make_data's GAE pass with value normalisation: raw targets and advantages under the COMMITTED table plus the targets'
+        moments (ppo_td_gae_vnorm), S_v with them folded in and its table into the scratch pair (ppo_value_norm_merge; all
+        ranks' sets in rank order), and the targets normalised under the scratch table (ppo_value_norm_apply).  Nothing
+        committed is written, so it is idempotent on a finished rollout."""
+        T, n = self.rollout_size, int(self.args.num_envs)
+        p = lambda x: C.c_void_p(x.data_ptr())   # noqa: E731
+        _lib.check(self._lib.ppo_td_gae_vnorm(
+            p(self.all_reward), p(values[:T]), p(values[1:]), p(done_f), p(self._value_table), C.c_float(self.gamma),
+            C.c_float(self.lmbda), C.c_int64(T), C.c_int64(n), p(self._target), p(self.all_advantage), p(self._value_sets),
+            C.c_int(mode), _lib.stream_ptr()), "ppo_td_gae_vnorm")
+        sets = self._value_sets
+        if self.world_size > 1:
+            import torch.distributed as dist
+            src = sets.cpu() if dist.get_backend() == "gloo" else sets
+            parts = [torch.empty_like(src) for _ in range(self.world_size)]
+            dist.all_gather(parts, src)
+            sets = torch.cat(parts).to(self.device)
+            self._keep_value_sets = sets                            # alive until the stream has consumed it
+        _lib.check(self._lib.ppo_value_norm_merge(p(self._value_stats), p(sets), C.c_int64(sets.shape[0]),
+                                                  p(self._value_stats_next), p(self._value_table_next), _lib.stream_ptr()),
+                   "ppo_value_norm_merge")
+        _lib.check(self._lib.ppo_value_norm_apply(p(self._target), C.c_int64(T * n), p(self._value_table_next),
+                                                  p(self._target_norm), _lib.stream_ptr()), "ppo_value_norm_apply")
+
+    def _commit_value_stats(self):
+        """S_v <- scratch, table <- scratch table: the next make_data denormalises under the table this update trained on."""
+        self._value_stats.copy_(self._value_stats_next)
+        self._value_table.copy_(self._value_table_next)
+
     # ppo.py:230 replaces the whole [T,N,1] buffer by the LAST step's [N,1] mask after every step
     # (Q1).  reset_buf only changes inside env.step, so deriving the mask on demand is the same
     # thing without two tiny launches per step; an explicit assignment (tests) overrides it.
@@ -372,17 +474,21 @@ class PPO:
             if n < 512 and T >= 1024:
                 mode |= 4                                           # PPO_GAE_SCAN: few envs x long rollout
             done_f = done.to(torch.float32).contiguous()
-            _lib.check(self._lib.ppo_td_gae(
-                C.c_void_p(self.all_reward.data_ptr()), C.c_void_p(values[:T].data_ptr()),
-                C.c_void_p(values[1:].data_ptr()), C.c_void_p(done_f.data_ptr()),
-                C.c_float(self.gamma), C.c_float(self.lmbda), C.c_int64(T), C.c_int64(n),
-                C.c_void_p(self._target.data_ptr()), C.c_void_p(self.all_advantage.data_ptr()),
-                C.c_int(mode), _lib.stream_ptr()), "ppo_td_gae")
+            if self.normalize_value:
+                self._td_gae_vnorm(values, done_f, mode)            # `values` are normalised-unit outputs: denormalised there
+            else:
+                _lib.check(self._lib.ppo_td_gae(
+                    C.c_void_p(self.all_reward.data_ptr()), C.c_void_p(values[:T].data_ptr()),
+                    C.c_void_p(values[1:].data_ptr()), C.c_void_p(done_f.data_ptr()),
+                    C.c_float(self.gamma), C.c_float(self.lmbda), C.c_int64(T), C.c_int64(n),
+                    C.c_void_p(self._target.data_ptr()), C.c_void_p(self.all_advantage.data_ptr()),
+                    C.c_int(mode), _lib.stream_ptr()), "ppo_td_gae")
             self._keep = (values, done_f)                           # alive until the stream has consumed them
             if self.normalize_advantage:
                 self._normalize_advantage()
         obs = self._obs_norm_ring[:T] if self.normalize_obs else self.all_obs
-        return obs, self.all_acts, self.all_log_prob, self._target, self.all_advantage
+        target = self._target_norm if self.normalize_value else self._target
+        return obs, self.all_acts, self.all_log_prob, target, self.all_advantage
 
     def _normalize_advantage(self):
         """Opt-in (`normalize_advantage`): adv <- (adv - mean) / (std + 1e-8) over the whole rollout of
@@ -422,6 +528,8 @@ class PPO:
             self._update_torch(obs, action, old_log_prob, target, advantage)
         if self.normalize_obs:
             self._merge_obs_stats()                                 # after update k: the statistics of rollout k + 1
+        if self.normalize_value:
+            self._commit_value_stats()                              # after update k: the table make_data k + 1 denormalises with
 
     def _update_torch(self, obs, action, old_log_prob, target, advantage):
         for _ in range(self.epoch):
@@ -885,6 +993,8 @@ class PPO:
         sd = {k: v.detach().clone().contiguous() for k, v in self.net.state_dict().items()}
         if self.normalize_obs:                                      # only then: otherwise the file is the reference's
             sd["obs_rms.mean"], sd["obs_rms.var"], sd["obs_rms.count"] = self.obs_mean, self.obs_var, self.obs_count
+        if self.normalize_value:
+            sd["value_rms.mean"], sd["value_rms.var"], sd["value_rms.count"] = self.value_mean, self.value_var, self.value_count
         torch.save(sd, path)
 
     def generate_video(self):

@@ -57,6 +57,9 @@ extern "C" {
 #define FLY_OBS_NORM_TABLE 147   /* observation normalisation table: mean[73] | rstd[73] | clip (f32) */
 #define FLY_OBS_NORM_SET 147     /* one set of statistics or moments: count | mean[73] | var or M2[73] (f64) */
 #define FLY_OBS_NORM_SETS 256    /* moment sets ppo_obs_norm_pass writes (one per workgroup) */
+#define FLY_VALUE_NORM_TABLE 4   /* value normalisation table: m | s | r | 0 (f32) */
+#define FLY_VALUE_NORM_SET 3     /* one set of value statistics or moments: count | mean | var or M2 (f64) */
+#define FLY_VALUE_NORM_SETS 256  /* moment sets ppo_td_gae_vnorm writes (one per workgroup) */
 #define FLY_DR_PARAMS 6   /* kp, kd, effort, mass (+ inertia), mu, gravity: multipliers of the FlyConfig values */
 #define FLY_DR_ROW 8      /* per-env row of the randomisation table, f32: m[6] | draw count (int32 bits) | 0 */
 
@@ -209,6 +212,32 @@ int ppo_obs_norm_pass(const float* ring, int64_t rows, int64_t count_from, const
                       void* stream);
 int ppo_obs_norm_merge(double* stats, float* table, const double* sets, int64_t k, float clip, void* stream);
 int fly_set_obs_norm(FlyHandle h, const float* table);
+
+/* Running value normalisation (opt-in, PPO --normalize_value).  The critic regresses on TD targets
+ * kept at zero mean / unit variance by running statistics; its outputs are mapped back to reward units where they meet rewards.
+ *   table f32 [FLY_VALUE_NORM_TABLE] = m | s | r | 0 with m = (float) mean, s = (float) sqrt(var + 1e-5),
+ *     r = (float) (1 / sqrt(var + 1e-5)), each computed in float64 and rounded once.  A critic output v becomes
+ *     vd = v * s + m and a target tg becomes y = (tg - m) * r: two separately rounded fp32 ops each, no fma and no clamp
+ *     (float32 numpy / torch reproduce both bit for bit; NaN passes through).
+ *   stats f64 [FLY_VALUE_NORM_SET] = count | mean | population var: the running statistics of the targets (initially 0 | 0 | 1).
+ *
+ * ppo_td_gae_vnorm: ppo_td_gae (same recurrence, same mode flags, same per-element ops in the same order) with v and v_next
+ *   replaced by their values under `table`, so target_out and adv_out are in reward units; under m = 0, s = 1 they are
+ *   ppo_td_gae's bit for bit.  Also the float64 moments (count | mean | M2) of all T x N targets, one set per workgroup in
+ *   sets f64 [FLY_VALUE_NORM_SETS][FLY_VALUE_NORM_SET] (sets over nothing have count 0).  Per-lane Welford updates and a
+ *   fixed combination tree, no atomics: deterministic.
+ * ppo_value_norm_merge: combines sets[0 .. k-1] in order (Chan's parallel update; empty sets are skipped), folds the result
+ *   into a copy of stats_in and writes that copy to stats_out and its table to table_out.  stats_in is NOT written (and must
+ *   not overlap stats_out): the caller commits by copying stats_out / table_out over its running pair when it chooses to.
+ *   One workgroup, no host sync; data-parallel callers gather every rank's sets and pass them in rank order, so all ranks
+ *   hold bit-identical statistics.
+ * ppo_value_norm_apply: out[i] = (target[i] - m) * r for n elements; `target` is only read, out must not alias it. */
+int ppo_td_gae_vnorm(const float* reward, const float* v, const float* v_next, const float* done, const float* table,
+                     float gamma, float lambda, int64_t T, int64_t N, float* target_out, float* adv_out, double* sets,
+                     int mode_flags, void* stream);
+int ppo_value_norm_merge(const double* stats_in, const double* sets, int64_t k, double* stats_out, float* table_out,
+                         void* stream);
+int ppo_value_norm_apply(const float* target, int64_t n, const float* table, float* out, void* stream);
 
 /* Per-env physics domain randomisation (opt-in).  The reference has none: every env of a batch runs
  * the one parameter set of the config.  With a table registered, env e runs FlyDyn on its own constants

@@ -9,6 +9,9 @@ Same flags (`--sim_device --compute_device_id --graphics_device_id --num_envs --
 `--normalize_obs` (running mean / std normalisation of the policy input, rl_games' normalize_input; off by default) with
 `--obs_clip` (the bound of a normalised input, default 5.0): the statistics are saved with the checkpoint as obs_rms.* and
 loaded with it; such a checkpoint needs `--normalize_obs` to load.
+`--normalize_value` (running mean / std normalisation of the critic's regression targets; off by default): the critic's
+outputs are mapped back to reward units wherever they meet rewards; the statistics are saved with the checkpoint as
+value_rms.* and loaded with it; such a checkpoint needs `--normalize_value` to load.
 `--randomize` (per-env physics domain randomisation, off by default): each env runs on its own multipliers of kp, kd, effort,
 mass (and inertia), mu and gravity, drawn from `--dr_<name> LO HI` at every reset of that env with seed `--dr_seed` (default
 `--seed`; rank r adds r * 0x9E3779B9).  A property of the env: nothing of it goes into the checkpoint.
@@ -64,6 +67,10 @@ def parse_args(argv=None):
     parser.add_argument('--normalize_obs', action='store_true',
                         help='normalise the policy input by running mean / std of the observations, clamped to +-obs_clip '
                              '(rl_games normalize_input; not in the reference; off by default)')
+    parser.add_argument('--normalize_value', action='store_true',
+                        help='the critic regresses on TD targets normalised by their running mean / std, and its outputs are '
+                             'mapped back to reward units for the TD target and GAE (rl_games normalize_value, without its clamp; '
+                             'not in the reference; off by default)')
     parser.add_argument('--obs_clip', type=float, default=5.0, help='bound of a normalised observation (with --normalize_obs)')
     parser.add_argument('--randomize', action='store_true',
                         help='per-env physics domain randomisation, redrawn at every reset of the env (Isaac Gym actor-property '
