@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include "flyhip.h"
 #include "domain_rand.h"
+#include "launch.h"
 
 namespace {
 

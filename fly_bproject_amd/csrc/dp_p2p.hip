@@ -20,6 +20,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "flyhip.h"
+#include "launch.h"
 
 namespace {
 

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "flyhip.h"
+#include "launch.h"
 
 namespace {
 

@@ -18,6 +18,7 @@
 #include <stdint.h>
 #include "flyhip.h"
 #include "dqn_layout.h"
+#include "launch.h"
 
 namespace {
 
@@ -466,13 +467,7 @@ extern "C" hipError_t flyhip_launch_dqn_grad_w(const float* x, const float* h1, 
     T.l[3] = T.l[2];
     // dynamic LDS: two buffers of the largest layer's chunk: 2 x 32 x (260 + 260) floats = 130 KiB
     const size_t lds_bytes = sizeof(float) * 2 * GW_ROWS * (DQN_H + GW_PAD + DQN_H + GW_PAD);
-    {       // (per launch: the attribute belongs to the CURRENT device)
-        hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(dqn_grad_w_kernel),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (ea != hipSuccess) return ea;
-    }
-    hipLaunchKernelGGL(dqn_grad_w_kernel, dim3(first), dim3(GW_THREADS), lds_bytes, (hipStream_t)stream, T, (long)n);
-    hipError_t e = hipGetLastError();
+    hipError_t e = launch_kernel<dqn_grad_w_kernel>(first, GW_THREADS, lds_bytes, stream, T, (long)n);
     if (e != hipSuccess || !(accumulate & 2)) return e;
     hipLaunchKernelGGL(dqn_grad_reduce_kernel, dim3(DQ_RED_BLOCKS), dim3(64 * DQ_RED_WAVES), 0, (hipStream_t)stream, T, grad, 0);
     return hipGetLastError();
@@ -494,14 +489,16 @@ extern "C" hipError_t flyhip_launch_dqn_adam(float* P, float* PF, float* PT, flo
 }
 
 // ---- the fused update: dqn_chain_kernel + dqn_dw2_kernel + the fixed-order reduction of their per-workgroup slabs -----------------
-static int dqn_cus()
+// the fixed-order reduction of the fused kernels' slabs (one per workgroup and layer, at ws1 / ws2 / ws3) into `grad`
+static hipError_t dqn_reduce_slabs(float* ws1, float* ws2, float* ws3, int grid, float* grad, void* stream)
 {
-    static int cus[16] = {0};        // per DEVICE: a process may drive more than one
-    int dev = 0;
-    hipDeviceProp_t pr;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 256;
-    if (!cus[dev]) cus[dev] = hipGetDeviceProperties(&pr, dev) == hipSuccess ? pr.multiProcessorCount : 256;
-    return cus[dev];
+    GradWTable T;
+    float* part[3] = {ws1, ws2, ws3};
+    const int N[3] = {DQN_H, DQN_H, DQN_OUT};
+    const int KP[3] = {DQN_IN_PAD, DQN_H, DQN_H};
+    fill_slab_table(T, N, KP, part, grid, 0);
+    hipLaunchKernelGGL(dqn_grad_reduce_kernel, dim3(DQ_RED_BLOCKS), dim3(64 * DQ_RED_WAVES), 0, (hipStream_t)stream, T, grad, 0);
+    return hipGetLastError();
 }
 
 static unsigned long long* g_dqn_stamps = nullptr;       // diagnostics (tools/stamp_dqn.py): u64 [workgroups][64], normally null
@@ -509,7 +506,7 @@ extern "C" void flyhip_debug_set_dqn_stamps(unsigned long long* p) { g_dqn_stamp
 // measurement only (bench.py times the launches one by one): bit 0 chain kernel, bit 1 dW2 kernel, bit 2 slab reduction; 7 = the update
 static int g_dqn_phases = 7;
 extern "C" void flyhip_debug_set_dqn_fused_phases(int mask) { g_dqn_phases = mask & 7; }
-extern "C" int64_t flyhip_dqn_fused_workspace_floats(void) { return (int64_t)dqn_cus() * DQN_PACKED_FLOATS; }
+extern "C" int64_t flyhip_dqn_fused_workspace_floats(void) { return (int64_t)device_cus() * DQN_PACKED_FLOATS; }
 extern "C" int64_t flyhip_dqn_fused_image_halves(int64_t rows) { return (rows / BM) * 2 * (int64_t)DF_IMAGE_HALVES; }
 
 extern "C" hipError_t flyhip_launch_dqn_fused_update(const float* P, const uint16_t* QB, const uint16_t* QTB, const float* P_tgt,
@@ -519,48 +516,27 @@ extern "C" hipError_t flyhip_launch_dqn_fused_update(const float* P, const uint1
 {
     const long tiles_per = n / BM, ntiles = (long)S * tiles_per;
     if (ntiles <= 0 || ntiles + 4096 >= (1L << 31)) return hipErrorInvalidValue;          // the kernels count tiles in 32 bits
-    const int cus = dqn_cus();
+    const int cus = device_cus();
     const int grid = (int)(ntiles < cus ? ntiles : cus);
-    {       // (per launch: the attribute belongs to the CURRENT device)
-        hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(dqn_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            DF_LDS_BYTES);
-        if (ea != hipSuccess) return ea;
-        ea = hipFuncSetAttribute(reinterpret_cast<const void*>(dqn_dw2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, DW2_LDS_BYTES);
-        if (ea != hipSuccess) return ea;
-    }
     float* ws1 = workspace;
     float* ws2 = ws1 + (long)cus * DF_STRIDE1;
     float* ws3 = ws2 + (long)cus * DF_STRIDE2;
-    hipError_t e = hipSuccess;
     if (g_dqn_phases & 1) {
-        hipLaunchKernelGGL(dqn_chain_kernel, dim3(grid), dim3(THREADS), DF_LDS_BYTES, (hipStream_t)stream, P, QB, QTB, P_tgt, QB_tgt,
-                           static_cast<const DqnChunk*>(chunks), S, tiles_per, discount, inv_B, images, ws1, ws2, ws3, loss_part,
-                           g_dqn_stamps, rows_aligned16);
-        e = hipGetLastError();
+        hipError_t e = launch_kernel<dqn_chain_kernel>(grid, THREADS, DF_LDS_BYTES, stream, P, QB, QTB, P_tgt, QB_tgt,
+                                                       static_cast<const DqnChunk*>(chunks), S, tiles_per, discount, inv_B, images, ws1, ws2,
+                                                       ws3, loss_part, g_dqn_stamps, rows_aligned16);
         if (e != hipSuccess) return e;
     }
     if (g_dqn_phases & 2) {
-        hipLaunchKernelGGL(dqn_dw2_kernel, dim3(grid), dim3(THREADS), DW2_LDS_BYTES, (hipStream_t)stream, images, ntiles, ws2);
-        e = hipGetLastError();
+        hipError_t e = launch_kernel<dqn_dw2_kernel>(grid, THREADS, DW2_LDS_BYTES, stream, images, ntiles, ws2);
         if (e != hipSuccess) return e;
     }
     if (!(g_dqn_phases & 4)) return hipSuccess;
-    GradWTable T;
-    float* part[3] = {ws1, ws2, ws3};
-    const int N[3] = {DQN_H, DQN_H, DQN_OUT};
-    const int KP[3] = {DQN_IN_PAD, DQN_H, DQN_H};
-    for (int l = 0; l < 3; ++l) {
-        T.l[l].dz = nullptr; T.l[l].a = nullptr; T.l[l].partial = part[l];
-        T.l[l].N = N[l]; T.l[l].Ka = KP[l]; T.l[l].KP = KP[l]; T.l[l].wgs = grid; T.l[l].first_block = 0; T.l[l].accumulate = 0;
-        T.l[l].chunked = 0;
-    }
-    T.l[3] = T.l[2];
-    hipLaunchKernelGGL(dqn_grad_reduce_kernel, dim3(DQ_RED_BLOCKS), dim3(64 * DQ_RED_WAVES), 0, (hipStream_t)stream, T, grad, 0);
-    return hipGetLastError();
+    return dqn_reduce_slabs(ws1, ws2, ws3, grid, grad, stream);
 }
 
 // ---- the same update in the fp16x2 arithmetic (dqn_fused_h2.inc): weight planes + scales, chain, dW2, slab reduction, next scales -----
-extern "C" int64_t flyhip_dqn_fused_h2_workspace_floats(void) { return (int64_t)dqn_cus() * (DQN_PACKED_FLOATS + H2_NACT_CLASSES); }
+extern "C" int64_t flyhip_dqn_fused_h2_workspace_floats(void) { return (int64_t)device_cus() * (DQN_PACKED_FLOATS + H2_NACT_CLASSES); }
 extern "C" int64_t flyhip_dqn_fused_h2_image_halves(int64_t rows) { return (rows / BM) * 2 * (int64_t)DH_IMAGE_HALVES; }
 
 // flags: bit 0 = leave the lagged scales as they are (tests: run-to-run comparisons), bit 1 = calibration pass (no dW2, no
@@ -573,15 +549,8 @@ extern "C" hipError_t flyhip_launch_dqn_fused_update_h2(const float* P, uint16_t
 {
     const long tiles_per = n / BM, ntiles = (long)S * tiles_per;
     if (ntiles <= 0 || ntiles + 4096 >= (1L << 31)) return hipErrorInvalidValue;
-    const int cus = dqn_cus();
+    const int cus = device_cus();
     const int grid = (int)(ntiles < cus ? ntiles : cus);
-    {
-        hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(dqn_chain_h2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            DH_LDS_BYTES);
-        if (ea != hipSuccess) return ea;
-        ea = hipFuncSetAttribute(reinterpret_cast<const void*>(dqn_dw2r_h2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, DW2R_LDS_BYTES);
-        if (ea != hipSuccess) return ea;
-    }
     float* ws1 = workspace;
     float* ws2 = ws1 + (long)cus * DF_STRIDE1;
     float* ws3 = ws2 + (long)cus * DF_STRIDE2;
@@ -591,31 +560,18 @@ extern "C" hipError_t flyhip_launch_dqn_fused_update_h2(const float* P, uint16_t
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (g_dqn_phases & 1) {
-        hipLaunchKernelGGL(dqn_chain_h2_kernel, dim3(grid), dim3(THREADS), DH_LDS_BYTES, st, P, QH, QTH, P_tgt, QH_tgt, fsc,
-                           static_cast<const DqnChunk*>(chunks), S, tiles_per, discount, inv_B, images, ws1, ws2, ws3, wsmax, loss_part,
-                           g_dqn_stamps, rows_aligned16);
-        e = hipGetLastError();
+        e = launch_kernel<dqn_chain_h2_kernel>(grid, THREADS, DH_LDS_BYTES, stream, P, QH, QTH, P_tgt, QH_tgt, fsc,
+                                               static_cast<const DqnChunk*>(chunks), S, tiles_per, discount, inv_B, images, ws1, ws2, ws3,
+                                               wsmax, loss_part, g_dqn_stamps, rows_aligned16);
         if (e != hipSuccess) return e;
     }
     if (!(flags & 2)) {
         if (g_dqn_phases & 2) {
-            hipLaunchKernelGGL(dqn_dw2r_h2_kernel, dim3(grid), dim3(THREADS), DW2R_LDS_BYTES, st, images, ntiles, P, fsc, ws2);
-            e = hipGetLastError();
+            e = launch_kernel<dqn_dw2r_h2_kernel>(grid, THREADS, DW2R_LDS_BYTES, stream, images, ntiles, P, fsc, ws2);
             if (e != hipSuccess) return e;
         }
         if (g_dqn_phases & 4) {
-            GradWTable T;
-            float* part[3] = {ws1, ws2, ws3};
-            const int N[3] = {DQN_H, DQN_H, DQN_OUT};
-            const int KP[3] = {DQN_IN_PAD, DQN_H, DQN_H};
-            for (int l = 0; l < 3; ++l) {
-                T.l[l].dz = nullptr; T.l[l].a = nullptr; T.l[l].partial = part[l];
-                T.l[l].N = N[l]; T.l[l].Ka = KP[l]; T.l[l].KP = KP[l]; T.l[l].wgs = grid; T.l[l].first_block = 0; T.l[l].accumulate = 0;
-                T.l[l].chunked = 0;
-            }
-            T.l[3] = T.l[2];
-            hipLaunchKernelGGL(dqn_grad_reduce_kernel, dim3(DQ_RED_BLOCKS), dim3(64 * DQ_RED_WAVES), 0, st, T, grad, 0);
-            e = hipGetLastError();
+            e = dqn_reduce_slabs(ws1, ws2, ws3, grid, grad, stream);
             if (e != hipSuccess) return e;
         }
     }

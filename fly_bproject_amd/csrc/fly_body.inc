@@ -5,7 +5,7 @@ constexpr int LANES_PER_ENV = 8;
 constexpr int BLOCK = 256;
 constexpr int ENVS_PER_BLOCK = BLOCK / LANES_PER_ENV;
 
-enum : int { PH_SCALE = 1, PH_RESET = 2, PH_INTEGRATE = 4, PH_OBS = 8, PH_REWARD = 16, PH_PROGRESS = 32 };
+// the phase bits PH_* (the template argument PH below) are declared in launch.h, for the host side too
 
 template <int CTRL>
 __device__ __forceinline__ float dpp_f(float x)

@@ -26,6 +26,7 @@
 #include <type_traits>
 #include "flyhip.h"
 #include "domain_rand.h"
+#include "launch.h"
 
 namespace {
 
@@ -57,39 +58,18 @@ inline int grid_for(int n) { return (n + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK; }
 
 }  // namespace
 
-// Launchers used by flyhip_abi.hip
-#define FLY_LAUNCH(PH)                                                                            \
-    hipLaunchKernelGGL((fly_kernel<PH>), dim3(grid_for(n)), dim3(BLOCK), 0, (hipStream_t)stream, \
-                       dcfg, actions, *b)
-
-#define FLY_DR_LAUNCH(PH)                                                                            \
-    hipLaunchKernelGGL((fly_dr_kernel<PH>), dim3(grid_for(n)), dim3(BLOCK), 0, (hipStream_t)stream, \
-                       dcfg, actions, *b)
-
 // dr: launch the randomising instantiation (the table registered in dcfg's slot); the phase sets that neither reset nor integrate
 // have none and run the plain kernel
 extern "C" hipError_t flyhip_launch_env(int phases, const FlyConfig* dcfg, int n, const float* actions,
                                         const FlyBuffers* b, void* stream, int dr)
 {
-    if (dr) {
-        switch (phases) {
-        case PH_SCALE | PH_RESET | PH_INTEGRATE | PH_OBS | PH_PROGRESS | PH_REWARD:
-            FLY_DR_LAUNCH(PH_SCALE | PH_RESET | PH_INTEGRATE | PH_OBS | PH_PROGRESS | PH_REWARD); return hipGetLastError();
-        case PH_RESET: FLY_DR_LAUNCH(PH_RESET); return hipGetLastError();
-        case PH_INTEGRATE: FLY_DR_LAUNCH(PH_INTEGRATE); return hipGetLastError();
-        default: break;
-        }
-    }
-    switch (phases) {
-    case PH_SCALE | PH_RESET | PH_INTEGRATE | PH_OBS | PH_PROGRESS | PH_REWARD:
-        FLY_LAUNCH(PH_SCALE | PH_RESET | PH_INTEGRATE | PH_OBS | PH_PROGRESS | PH_REWARD); break;
-    case PH_SCALE: FLY_LAUNCH(PH_SCALE); break;
-    case PH_RESET: FLY_LAUNCH(PH_RESET); break;
-    case PH_INTEGRATE: FLY_LAUNCH(PH_INTEGRATE); break;
-    case PH_OBS: FLY_LAUNCH(PH_OBS); break;
-    case PH_REWARD: FLY_LAUNCH(PH_REWARD); break;
-    case PH_REWARD | PH_PROGRESS: FLY_LAUNCH(PH_REWARD | PH_PROGRESS); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    constexpr int PH_ALL = PH_SCALE | PH_RESET | PH_INTEGRATE | PH_OBS | PH_PROGRESS | PH_REWARD;
+    const dim3 grid(grid_for(n));
+    if (dr && (phases & (PH_RESET | PH_INTEGRATE)))     // of the phase sets that exist: the full step, PH_RESET, PH_INTEGRATE
+        return with_int<PH_ALL, PH_RESET, PH_INTEGRATE>(phases, [&](auto ph) {
+            return launch_kernel<fly_dr_kernel<ph.value>>(grid, BLOCK, 0, stream, dcfg, actions, *b);
+        });
+    return with_int<PH_ALL, PH_SCALE, PH_RESET, PH_INTEGRATE, PH_OBS, PH_REWARD, PH_REWARD | PH_PROGRESS>(phases, [&](auto ph) {
+        return launch_kernel<fly_kernel<ph.value>>(grid, BLOCK, 0, stream, dcfg, actions, *b);
+    });
 }

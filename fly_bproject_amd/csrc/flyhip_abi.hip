@@ -1,6 +1,7 @@
 // flyhip_abi.hip — the extern "C" surface declared in include/flyhip.h.
-// Argument checking, handle lifetime and error strings live here; kernels live in fly_env.hip
-// and ppo_kernels.hip.  Nothing here synchronises the host or allocates caller tensors.
+// Argument checking, handle lifetime and error strings live here; the kernels and their launchers
+// (flyhip_launch_*) live in the other .hip files of this directory and are declared, once, in
+// launch.h.  Nothing here synchronises the host or allocates caller tensors.
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <stdint.h>
@@ -10,125 +11,8 @@
 #include "flyhip.h"
 #include "obs_norm.h"
 #include "domain_rand.h"
+#include "launch.h"
 #include <math.h>
-
-extern "C" hipError_t flyhip_launch_env(int phases, const FlyConfig* dcfg, int n, const float* actions,
-                                        const FlyBuffers* b, void* stream, int dr);
-extern "C" hipError_t flyhip_launch_sample_logprob(const float* mu, const float* var, const float* eps,
-                                                   float* act_out, float* logp_out, int64_t n, void* stream);
-extern "C" hipError_t flyhip_launch_td_gae(const float* reward, const float* v, const float* v_next,
-                                           const float* done, float gamma, float lambda, int64_t T, int64_t N,
-                                           float* target_out, float* adv_out, int mode, void* stream);
-
-extern "C" hipError_t flyhip_launch_mlp_forward(const float* P, const float* PF, const float* x, int64_t n, float* mu_out,
-                                                float* v_out, float* out_save, float* h1_save, float* h2_save,
-                                                float* h3_save, const uint16_t* PB, void* stream);
-
-extern "C" hipError_t flyhip_launch_mlp_backward_dx(const float* PT, const float* out_saved, const float* h1,
-                                                    const float* h2, const float* h3, const float* action,
-                                                    const float* old_logp, const float* adv, const float* target,
-                                                    const float* var, int64_t n, float inv_batch, float clip,
-                                                    float* dz4, float* dz3, float* dz2, float* dz1, float* loss_part,
-                                                    const uint16_t* PTB, void* stream);
-extern "C" hipError_t flyhip_launch_dqn_forward(const float* P, const float* PF, const float* x, int64_t n, float* q_out,
-                                                void* stream);
-extern "C" hipError_t flyhip_launch_dqn_act(const float* P, const float* PF, const float* x, int64_t n, const float* coin_u,
-                                            const float* rand_u, float epsilon, float* act_out, float* q_out, void* stream);
-extern "C" hipError_t flyhip_launch_dqn_td(const float* P, const float* PF, const float* PT, const float* P_tgt,
-                                           const float* PF_tgt, const float* obs, const float* next_obs, const float* act,
-                                           const float* reward, const float* done, int64_t n, float discount, float inv_B,
-                                           float* h1, float* h2, float* dz3, float* dz2, float* dz1, float* loss_part,
-                                           void* stream);
-extern "C" int64_t flyhip_dqn_grad_workspace_floats(void);
-extern "C" hipError_t flyhip_launch_dqn_grad_w(const float* x, const float* h1, const float* h2, const float* dz1,
-                                               const float* dz2, const float* dz3, int64_t n, float* workspace, float* grad,
-                                               int accumulate, void* stream);
-extern "C" hipError_t flyhip_launch_dqn_adam(float* P, float* PF, float* PT, float* P_tgt, float* PF_tgt, const int* idx_f,
-                                             const int* idx_t, const float* G, const float* mask, float* m, float* v,
-                                             int* step, float lr, float beta1, float beta2, float eps, float tau, uint16_t* QB, uint16_t* QTB, uint16_t* QB_tgt, const int* idx_fb, const int* idx_tb,
-                                             const int* grad_invalid, void* stream);
-extern "C" hipError_t flyhip_p2p_alloc(int64_t n_floats, void** out);
-extern "C" hipError_t flyhip_launch_p2p_allreduce(float* G, int64_t n, void* const* bases, int rank, int world,
-                                                  uint32_t epoch, int* err, int64_t fail_slot, void* stream);
-extern "C" int64_t flyhip_mlp_grad_workspace_floats(void);
-extern "C" int64_t flyhip_mlp_fused_workspace_floats(void);
-extern "C" hipError_t flyhip_launch_mlp_fused_grad(const float* P, const uint16_t* PB, const uint16_t* PTB, const float* x,
-                                                   int64_t n, const float* action, const float* old_logp, const float* adv,
-                                                   const float* target, const float* var, float inv_batch, float clip,
-                                                   float* workspace, float* grad_out, const float* norm_mask, float* norm_ws,
-                                                   int* norm_step, float* loss_part, float* const* dump, void* stream);
-extern "C" hipError_t flyhip_launch_mlp_grad_w(const float* x, const float* h1, const float* h2, const float* h3,
-                                               const float* dz1, const float* dz2, const float* dz3, const float* dz4,
-                                               int64_t n, float* workspace, float* grad_out, const float* norm_mask,
-                                               float* norm_ws, int* norm_step, const int* err, int gemm_b3, void* stream);
-extern "C" hipError_t flyhip_launch_mlp_adam(float* P, float* PF, float* PT, const int* idx_f, const int* idx_t,
-                                             const float* G, const float* mask, float* m,
-                                             float* v, int* step, float lr, float beta1, float beta2, float eps,
-                                             float max_norm, float grad_scale, float* norm_ws, int norm_ready,
-                                             uint16_t* PB, uint16_t* PTB, const int* idx_fb, const int* idx_tb,
-                                             int* step_out, const int* grad_invalid, uint16_t* PH, uint16_t* PTH,
-                                             float* h2_scales, int h2_period, void* stream);
-extern "C" hipError_t flyhip_launch_mlp_h2_rescale(const float* P, const int* idx_fb, const int* idx_tb, uint16_t* PH, uint16_t* PTH,
-                                                   float* h2_scales, void* stream);
-extern "C" int64_t flyhip_mlp_fused_h2_workspace_floats(void);
-extern "C" hipError_t flyhip_launch_mlp_fused_grad_h2(const float* P, const uint16_t* PH, const uint16_t* PTH, float* fsc, int* ovf,
-                                                      int freeze, const float* x, int64_t n, const float* action,
-                                                      const float* old_logp, const float* adv, const float* target, const float* var,
-                                                      float inv_batch, float clip, float* workspace, float* grad_out,
-                                                      const float* norm_mask, float* norm_ws, int* norm_step, float* loss_part,
-                                                      float* const* dump, void* stream);
-
-extern "C" hipError_t flyhip_launch_bookkeeping(const float* reward, int64_t n, float* score_acc, float score_scale,
-                                                float* action_var, int nvar, float var_decay, float var_min,
-                                                void* stream);
-
-extern "C" hipError_t flyhip_launch_dqn_eps_greedy(const float* q, const float* coin_u, const float* rand_u, float epsilon,
-                                                   int A, float* act_out, int64_t n, void* stream);
-extern "C" hipError_t flyhip_launch_dqn_huber_td(const float* q_table, const float* act, const float* reward,
-                                                 const float* q_next, const float* done, float discount, int A, int64_t B,
-                                                 float* dq, float* loss_part, void* stream);
-
-extern "C" hipError_t flyhip_launch_mlp_forward_sample(const float* P, const float* PF, const float* x, int64_t n,
-                                                       const float* eps, const float* var, int var_steps,
-                                                       float var_decay, float var_min, float* act_out,
-                                                       float* logp_out, float* mu_out, float* v_out, const uint16_t* PB,
-                                                       const int* var_base, void* stream);
-
-extern "C" hipError_t flyhip_launch_mlp_fwd_bwd(const float* P, const float* PF, const float* PT, const float* x, int64_t n,
-                                                float* out_save, float* h1_save, float* h2_save, float* h3_save,
-                                                const float* action, const float* old_logp, const float* adv,
-                                                const float* target, const float* var, float inv_batch, float clip,
-                                                float* dz4, float* dz3, float* dz2, float* dz1, float* loss_part,
-                                                int* flags, int epoch, int* err, const uint16_t* PB, const uint16_t* PTB,
-                                                int coherent, void* stream);
-extern "C" hipError_t flyhip_launch_rollout_all(const FlyConfig* dcfg, const FlyBuffers* b, const float* P, const float* PF,
-                                                float* obs_ring, int64_t n, const float* eps_all, const float* var,
-                                                float var_decay, float var_min, float* act_all, float* logp_all, float* v_ring,
-                                                float* reward_all, int T, const int* rows_applied, const uint16_t* PB,
-                                                int64_t* reset_rows, int64_t* progress_rows, void* stream,
-                                                unsigned long long* stamps, float* poses, int norm, int dr);
-extern "C" hipError_t flyhip_launch_render(const FlyConfig* dcfg, const float* poses, int frames, const FlyRenderConfig* rc,
-                                           uint32_t* rgba_out, uint8_t* id_out, void* stream);
-extern "C" hipError_t flyhip_launch_rollout_bookkeeping(const float* reward, int64_t rows, int64_t n, float* terms,
-                                                        float* score_acc, float score_scale, float* action_var, int nvar,
-                                                        float var_decay, float var_min, int* rows_applied, void* stream);
-extern "C" hipError_t flyhip_launch_rollout_step(const FlyConfig* dcfg, const FlyBuffers* b, const float* P, const float* PF,
-                                                 const float* x, int64_t n, const float* eps, const float* var, int var_steps,
-                                                 float var_decay, float var_min, float* act, float* logp, float* v_out,
-                                                 const uint16_t* PB, const int* var_base, void* stream, int norm, int dr);
-extern "C" hipError_t flyhip_launch_adv_stats(const float* adv, int64_t n, float* stats, void* stream);
-extern "C" hipError_t flyhip_launch_adv_apply(float* adv, int64_t n, const float* totals, float count, float eps, void* stream);
-extern "C" hipError_t flyhip_launch_obs_norm_pass(const float* ring, int64_t rows, int64_t count_from, const float* table,
-                                                  float* out, double* sets, void* stream);
-extern "C" hipError_t flyhip_launch_obs_norm_merge(double* stats, float* table, const double* sets, int64_t k, float clip,
-                                                   void* stream);
-extern "C" hipError_t flyhip_launch_td_gae_vnorm(const float* reward, const float* v, const float* v_next, const float* done,
-                                                 const float* table, float gamma, float lambda, int64_t T, int64_t N,
-                                                 float* target_out, float* adv_out, double* sets, int mode, void* stream);
-extern "C" hipError_t flyhip_launch_value_norm_merge(const double* stats_in, const double* sets, int64_t k, double* stats_out,
-                                                     float* table_out, void* stream);
-extern "C" hipError_t flyhip_launch_value_norm_apply(const float* target, int64_t n, const float* table, float* out, void* stream);
-extern "C" hipError_t flyhip_launch_dr_register(const FlyConfig* dcfg, int n, void* stream);
 
 struct FlyEnv {
     FlyConfig host;
@@ -154,8 +38,6 @@ int hip_fail(hipError_t e, const char* what)
 {
     return fail(FLY_E_HIP, "%s: %s", what, hipGetErrorString(e));
 }
-
-enum : int { PH_SCALE = 1, PH_RESET = 2, PH_INTEGRATE = 4, PH_OBS = 8, PH_REWARD = 16, PH_PROGRESS = 32 };
 
 int check_buffers(const FlyBuffers* b, int phases)
 {
@@ -762,13 +644,6 @@ int dqn_adam_soft_update(float* params, float* params_frag, float* params_t_frag
     return FLY_OK;
 }
 
-extern "C" int64_t flyhip_dqn_fused_workspace_floats(void);
-extern "C" int64_t flyhip_dqn_fused_image_halves(int64_t rows);
-extern "C" hipError_t flyhip_launch_dqn_fused_update(const float* P, const uint16_t* QB, const uint16_t* QTB, const float* P_tgt,
-                                                     const uint16_t* QB_tgt, const void* chunks, int S, int64_t n, float discount,
-                                                     float inv_B, uint16_t* images, float* workspace, float* grad, float* loss_part,
-                                                     int rows_aligned16, void* stream);
-
 int64_t dqn_fused_workspace_floats(void) { return flyhip_dqn_fused_workspace_floats(); }
 int64_t dqn_fused_image_halves(int64_t rows) { return flyhip_dqn_fused_image_halves(rows); }
 
@@ -786,13 +661,6 @@ int dqn_fused_update(const float* params, const uint16_t* params_b3, const uint1
     if (e != hipSuccess) return hip_fail(e, "dqn_fused_update launch");
     return FLY_OK;
 }
-
-extern "C" int64_t flyhip_dqn_fused_h2_workspace_floats(void);
-extern "C" int64_t flyhip_dqn_fused_h2_image_halves(int64_t rows);
-extern "C" hipError_t flyhip_launch_dqn_fused_update_h2(const float* P, uint16_t* QH, uint16_t* QTH, const float* P_tgt, uint16_t* QH_tgt,
-                                                        const int* idx_fb, const int* idx_tb, float* fsc, int* ovf, const void* chunks,
-                                                        int S, int64_t n, float discount, float inv_B, uint16_t* images, float* workspace,
-                                                        float* grad, float* loss_part, int rows_aligned16, int flags, void* stream);
 
 int64_t dqn_fused_h2_workspace_floats(void) { return flyhip_dqn_fused_h2_workspace_floats(); }
 int64_t dqn_fused_h2_image_halves(int64_t rows) { return flyhip_dqn_fused_h2_image_halves(rows); }

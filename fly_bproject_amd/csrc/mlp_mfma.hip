@@ -16,6 +16,9 @@
 //   mlp_fused_step.inc  ONE persistent launch per minibatch: forward, loss, dX chain and dW of every tile in the workgroup
 //                     that owns it (bf16x3; activations never leave the CU, dW accumulated in registers)
 //   mlp_adam.inc      clip_grad_norm_ + Adam on the packed parameters
+//   launch.h          host side of every launcher in this directory: the declarations of the flyhip_launch_* entry points,
+//                     with_bools / with_int (runtime flags -> template arguments; a new variant flag is one more argument there)
+//                     and launch_kernel
 //
 // The operand roles are fixed throughout: weights are the MFMA "A" operand, activations the "B"
 // operand, so a lane of a 32x32 result tile owns one batch row and groups of four consecutive
@@ -29,6 +32,7 @@
 #include "mlp_layout.h"
 #include "obs_norm.h"
 #include "domain_rand.h"
+#include "launch.h"
 
 namespace {
 
@@ -249,34 +253,6 @@ __global__ __launch_bounds__(THREADS, 1) void rollout_all_fs_kernel(
 
 }  // namespace
 
-// the normalising and / or randomising instantiations of rollout_all_fs_kernel (the table and the randomisation slot are read
-// through dcfg: the argument list is the plain one's)
-#define RAFS_OPT_PARAMS dim3 grid, hipStream_t stream, const FlyConfig* dcfg, const FlyBuffers* b, const float* P, const uint16_t* PB,      \
-                        float* obs_ring, long n, const float* eps_all, const float* var, float var_decay, float var_min, float* act_all,  \
-                        float* logp_all, float* v_ring, float* reward_all, int T, int64_t* reset_rows, int64_t* progress_rows, void* aux
-#define RAFS_OPT_ARGS grid, stream, dcfg, b, P, PB, obs_ring, n, eps_all, var, var_decay, var_min, act_all, logp_all, v_ring, reward_all, T, \
-                      reset_rows, progress_rows, aux
-template <bool MULTI, bool REC, bool NORM, bool DR>
-static hipError_t launch_rollout_all_fs_opt(RAFS_OPT_PARAMS)
-{
-    const int bytes = FR_LDS_BYTES + (NORM ? NORM_LDS_FLOATS * 4 : 0);
-    static_assert(FR_LDS_BYTES % 4 == 0, "the table follows the image");
-    hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(rollout_all_fs_kernel<false, MULTI, REC, NORM, DR>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (ea != hipSuccess) return ea;
-    hipLaunchKernelGGL((rollout_all_fs_kernel<false, MULTI, REC, NORM, DR>), grid, dim3(THREADS), bytes, stream, dcfg, *b, P, PB, obs_ring,
-                       n, eps_all, var, var_decay, var_min, act_all, logp_all, v_ring, reward_all, T, reset_rows, progress_rows, aux);
-    return hipGetLastError();
-}
-template <bool NORM, bool DR>
-static hipError_t launch_rollout_all_fs_opt(bool multi, bool rec, RAFS_OPT_PARAMS)
-{
-    return multi ? (rec ? launch_rollout_all_fs_opt<true, true, NORM, DR>(RAFS_OPT_ARGS) : launch_rollout_all_fs_opt<true, false, NORM, DR>(RAFS_OPT_ARGS))
-                 : (rec ? launch_rollout_all_fs_opt<false, true, NORM, DR>(RAFS_OPT_ARGS) : launch_rollout_all_fs_opt<false, false, NORM, DR>(RAFS_OPT_ARGS));
-}
-#undef RAFS_OPT_PARAMS
-#undef RAFS_OPT_ARGS
-
 // poses (optional, device [T][FLY_POSE_FLOATS]): launch the REC instantiation of whichever kernel the shape selects -- recording
 // never changes the launch form.  The stamped diagnostic instantiation does not record.  norm: the NORM instantiation of the same
 // kernel (the table registered in dcfg's slot, fly_set_obs_norm); dr: its DR instantiation (fly_set_randomization); neither with
@@ -289,66 +265,36 @@ extern "C" hipError_t flyhip_launch_rollout_all(const FlyConfig* dcfg, const Fly
                                                 unsigned long long* stamps, float* poses, int norm, int dr)
 {
     const dim3 grid((unsigned)((n + BM - 1) / BM));
-    int cus = 256;
-    { int dev = 0; hipDeviceProp_t pr; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) cus = pr.multiProcessorCount; }
+    const int cus = device_cus();
     const bool one_per_cu = (int)grid.x <= cus;
-    const dim3 grid_fs((unsigned)((int)grid.x <= cus ? (int)grid.x : cus));   // the fused-style kernel walks its tiles itself
     const char* fs_env = getenv("FLY_ROLLOUT_FS");               // read per launch: the tests flip it inside one process
     const bool fs_off = fs_env != nullptr && fs_env[0] == '0';
     if (stamps && (poses || norm || dr)) return hipErrorInvalidValue;
     const bool rec = poses != nullptr;
     if (PB && n % BM == 0 && !fs_off) {       // the policy body in the fused step's style (A/B: FLY_ROLLOUT_FS=0); persistent over tiles
-        const bool multi = (int)grid.x > cus;
-        if (norm || dr) {
-#define RAFS_OPT(N_, D_) launch_rollout_all_fs_opt<N_, D_>(multi, rec, grid_fs, (hipStream_t)stream, dcfg, b, P, PB, obs_ring, (long)n, eps_all, \
-                                                           var, var_decay, var_min, act_all, logp_all, v_ring, reward_all, T, reset_rows,    \
-                                                           progress_rows, poses)
-            return norm && dr ? RAFS_OPT(true, true) : norm ? RAFS_OPT(true, false) : RAFS_OPT(false, true);
-#undef RAFS_OPT
-        }
-        const int si = (stamps ? 1 : 0) + (multi ? 2 : 0) + (rec ? 4 : 0);
-        const void* fn = si == 0 ? reinterpret_cast<const void*>(rollout_all_fs_kernel<false, false, false>)
-                       : si == 1 ? reinterpret_cast<const void*>(rollout_all_fs_kernel<true, false, false>)
-                       : si == 2 ? reinterpret_cast<const void*>(rollout_all_fs_kernel<false, true, false>)
-                       : si == 3 ? reinterpret_cast<const void*>(rollout_all_fs_kernel<true, true, false>)
-                       : si == 4 ? reinterpret_cast<const void*>(rollout_all_fs_kernel<false, false, true>)
-                                 : reinterpret_cast<const void*>(rollout_all_fs_kernel<false, true, true>);
-        {       // (per launch: the attribute belongs to the CURRENT device)
-            hipError_t ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BYTES);
-            if (ea != hipSuccess) return ea;
-        }
-#define RAFS_LAUNCH(S_, M_, R_)                                                                                                       \
-        hipLaunchKernelGGL((rollout_all_fs_kernel<S_, M_, R_>), grid_fs, dim3(THREADS), FR_LDS_BYTES, (hipStream_t)stream, dcfg, *b, P, \
-                           PB, obs_ring, (long)n, eps_all, var, var_decay, var_min, act_all, logp_all, v_ring, reward_all, T,         \
-                           reset_rows, progress_rows, rec ? (void*)poses : (void*)stamps)
-        if (si == 0) RAFS_LAUNCH(false, false, false); else if (si == 1) RAFS_LAUNCH(true, false, false);
-        else if (si == 2) RAFS_LAUNCH(false, true, false); else if (si == 3) RAFS_LAUNCH(true, true, false);
-        else if (si == 4) RAFS_LAUNCH(false, false, true); else RAFS_LAUNCH(false, true, true);
-#undef RAFS_LAUNCH
-        return hipGetLastError();
+        const dim3 grid_fs(one_per_cu ? grid.x : (unsigned)cus);     // the fused-style kernel walks its tiles itself
+        static_assert(FR_LDS_BYTES % 4 == 0, "the table follows the image");
+        // aux: the stamps or the pose record; the table and the randomisation slot are read through dcfg
+        auto fs = [&](void* aux, auto S, auto M, auto R, auto N, auto D) {
+            return launch_kernel<rollout_all_fs_kernel<S.value, M.value, R.value, N.value, D.value>>(
+                grid_fs, THREADS, FR_LDS_BYTES + (N.value ? NORM_LDS_FLOATS * 4 : 0), stream, dcfg, *b, P, PB, obs_ring, (long)n, eps_all,
+                var, var_decay, var_min, act_all, logp_all, v_ring, reward_all, T, reset_rows, progress_rows, aux);
+        };
+        constexpr std::false_type no{};
+        const bool multi = !one_per_cu;
+        if (stamps) return with_bools([&](auto M) { return fs(stamps, std::true_type{}, M, no, no, no); }, multi);   // records, normalises, randomises nothing
+        return with_bools([&](auto M, auto R, auto N, auto D) { return fs(poses, no, M, R, N, D); }, multi, rec, norm != 0, dr != 0);
     }
     if (stamps) return hipErrorInvalidValue;        // only the fused-style kernel has a stamped instantiation
-#define RA_K(B3_, WPS_, PF_, R_, N_, D_)                                                                                          \
-    hipLaunchKernelGGL((rollout_all_kernel<B3_, WPS_, R_, N_, D_>), grid, dim3(THREADS), 0, (hipStream_t)stream, dcfg, *b, P,          \
-                       (const void*)PF_, obs_ring, (long)n, eps_all, var, var_decay, var_min, act_all, logp_all, v_ring, reward_all, T, \
-                       rows_applied, reset_rows, progress_rows, poses)
-#define RA_LAUNCH_D(B3_, WPS_, PF_, D_)                                                                                            \
-    do {                                                                                                                           \
-        if (norm && rec) RA_K(B3_, WPS_, PF_, true, true, D_);                                                                     \
-        else if (norm) RA_K(B3_, WPS_, PF_, false, true, D_);                                                                      \
-        else if (rec) RA_K(B3_, WPS_, PF_, true, false, D_);                                                                       \
-        else RA_K(B3_, WPS_, PF_, false, false, D_);                                                                               \
-    } while (0)
-#define RA_LAUNCH(B3_, WPS_, PF_)                                                                                                  \
-    do {                                                                                                                           \
-        if (dr) RA_LAUNCH_D(B3_, WPS_, PF_, true); else RA_LAUNCH_D(B3_, WPS_, PF_, false);                                        \
-    } while (0)
-    if (PB) { if (one_per_cu) RA_LAUNCH(true, 1, PB); else RA_LAUNCH(true, 1, PB); }      // the bf16x3 body needs one wave per SIMD anyway
-    else { if (one_per_cu) RA_LAUNCH(false, 1, PF); else RA_LAUNCH(false, 2, PF); }
-#undef RA_LAUNCH
-#undef RA_LAUNCH_D
-#undef RA_K
-    return hipGetLastError();
+    auto ra = [&](auto B3, auto WPS, const void* pf) {
+        return with_bools([&](auto R, auto N, auto D) {
+            return launch_kernel<rollout_all_kernel<B3.value, WPS.value, R.value, N.value, D.value>>(
+                grid, THREADS, 0, stream, dcfg, *b, P, pf, obs_ring, (long)n, eps_all, var, var_decay, var_min, act_all, logp_all, v_ring,
+                reward_all, T, rows_applied, reset_rows, progress_rows, poses);
+        }, rec, norm != 0, dr != 0);
+    };
+    if (PB) return ra(std::true_type{}, int_c<1>{}, PB);        // the bf16x3 body needs one wave per SIMD anyway
+    return one_per_cu ? ra(std::false_type{}, int_c<1>{}, PF) : ra(std::false_type{}, int_c<2>{}, PF);
 }
 
 extern "C" hipError_t flyhip_launch_mlp_forward(const float* P, const float* PF, const float* x, int64_t n, float* mu_out,
@@ -467,14 +413,11 @@ extern "C" hipError_t flyhip_launch_mlp_fwd_bwd(const float* P, const float* PF,
     const bool b3 = PB && PTB;
     const void* pf = b3 ? (const void*)PB : (const void*)PF;
     const void* pt = b3 ? (const void*)PTB : (const void*)PT;
-#define FB_LAUNCH(B3_, COH_)                                                                                                   \
-    hipLaunchKernelGGL((mlp_fwd_bwd_kernel<false, B3_, COH_>), grid, dim3(THREADS), 0, (hipStream_t)stream, P, pf, pt, x,      \
-                       (long)n, out_save, h1_save, h2_save, h3_save, action, old_logp, adv, target, var, inv_batch, clip, dz4, \
-                       dz3, dz2, dz1, loss_part, flags, epoch, err, (unsigned long long*)nullptr, shift)
-    if (b3) { if (coherent) FB_LAUNCH(true, true); else FB_LAUNCH(true, false); }
-    else { if (coherent) FB_LAUNCH(false, true); else FB_LAUNCH(false, false); }
-#undef FB_LAUNCH
-    return hipGetLastError();
+    return with_bools([&](auto B3, auto COH) {
+        return launch_kernel<mlp_fwd_bwd_kernel<false, B3.value, COH.value>>(
+            grid, THREADS, 0, stream, P, pf, pt, x, (long)n, out_save, h1_save, h2_save, h3_save, action, old_logp, adv, target, var,
+            inv_batch, clip, dz4, dz3, dz2, dz1, loss_part, flags, epoch, err, (unsigned long long*)nullptr, shift);
+    }, b3, coherent != 0);
 }
 
 // diagnostic build with per-workgroup start/end stamps (tools/stamp_fwd_bwd.py); not part of the ABI header
@@ -499,23 +442,11 @@ extern "C" hipError_t flyhip_launch_rollout_step(const FlyConfig* dcfg, const Fl
                                                  const uint16_t* PB, const int* var_base, void* stream, int norm, int dr)
 {
     const dim3 grid((unsigned)((n + BM - 1) / BM));
-#define RS_K(B3_, N_, D_)                                                                                                           \
-    hipLaunchKernelGGL((rollout_step_kernel<B3_, N_, D_>), grid, dim3(THREADS), 0, (hipStream_t)stream, dcfg, *b, P,                \
-                       B3_ ? (const void*)PB : (const void*)PF, x, (long)n, eps, var, var_steps, var_decay, var_min, act, logp, v_out, \
-                       var_base)
-    if (dr) {
-        if (norm && PB) RS_K(true, true, true);
-        else if (norm) RS_K(false, true, true);
-        else if (PB) RS_K(true, false, true);
-        else RS_K(false, false, true);
-    } else {
-        if (norm && PB) RS_K(true, true, false);
-        else if (norm) RS_K(false, true, false);
-        else if (PB) RS_K(true, false, false);
-        else RS_K(false, false, false);
-    }
-#undef RS_K
-    return hipGetLastError();
+    return with_bools([&](auto B3, auto N, auto D) {
+        return launch_kernel<rollout_step_kernel<B3.value, N.value, D.value>>(
+            grid, THREADS, 0, stream, dcfg, *b, P, B3.value ? (const void*)PB : (const void*)PF, x, (long)n, eps, var, var_steps, var_decay,
+            var_min, act, logp, v_out, var_base);
+    }, PB != nullptr, norm != 0, dr != 0);
 }
 
 extern "C" int64_t flyhip_mlp_grad_workspace_floats(void)
@@ -555,27 +486,13 @@ extern "C" hipError_t flyhip_launch_mlp_grad_w(const float* x, const float* h1, 
     // dynamic LDS: two buffers of the largest layer's chunk (padded pitches): 2 x 32 x (136 + 264) floats = 100 KiB
     const size_t lds_bytes = sizeof(float) * 2 * GW_ROWS * (MLP_H2 + GW_PAD + MLP_H1 + GW_PAD);
     static_assert(MLP_H1 + GW_PAD + 96 <= MLP_H2 + GW_PAD + MLP_H1 + GW_PAD, "layer 1 chunk fits");
-    {       // (per launch: the attribute belongs to the CURRENT device)
-        hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_grad_w_kernel),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (ea != hipSuccess) return ea;
-    }
-    if (gemm_b3) {
-        // two buffers of three bf16 term planes of a chunk: layers 1 / 2 stage 16 rows x (288 + 160) columns (84 KiB),
-        // layer 3 32 rows x (160 + 160) (120 KiB, the largest), layer 4 32 rows x (32 + 160) (72 KiB)
-        const size_t b3_bytes = 2 * 3 * GB_ROWS_L3 * 2 * gb_pitch<MLP_H3>() * sizeof(u16);
-        static_assert(16 * (gb_pitch<MLP_H1>() + gb_pitch<MLP_H2>()) <= GB_ROWS_L3 * 2 * gb_pitch<MLP_H3>() &&
-                      GB_ROWS_L4 * (gb_pitch<MLP_OUT>() + gb_pitch<MLP_H3>()) <= GB_ROWS_L3 * 2 * gb_pitch<MLP_H3>(), "layer 3's chunk is the largest");
-        {       // (per launch: the attribute belongs to the CURRENT device)
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_grad_w_b3_kernel),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)b3_bytes);
-            if (ea != hipSuccess) return ea;
-        }
-        hipLaunchKernelGGL(mlp_grad_w_b3_kernel, dim3(first), dim3(GW_THREADS), b3_bytes, (hipStream_t)stream, T, (long)n);
-    } else {
-        hipLaunchKernelGGL(mlp_grad_w_kernel, dim3(first), dim3(GW_THREADS), lds_bytes, (hipStream_t)stream, T, (long)n);
-    }
-    hipError_t e = hipGetLastError();
+    // two buffers of three bf16 term planes of a chunk: layers 1 / 2 stage 16 rows x (288 + 160) columns (84 KiB),
+    // layer 3 32 rows x (160 + 160) (120 KiB, the largest), layer 4 32 rows x (32 + 160) (72 KiB)
+    const size_t b3_bytes = 2 * 3 * GB_ROWS_L3 * 2 * gb_pitch<MLP_H3>() * sizeof(u16);
+    static_assert(16 * (gb_pitch<MLP_H1>() + gb_pitch<MLP_H2>()) <= GB_ROWS_L3 * 2 * gb_pitch<MLP_H3>() &&
+                  GB_ROWS_L4 * (gb_pitch<MLP_OUT>() + gb_pitch<MLP_H3>()) <= GB_ROWS_L3 * 2 * gb_pitch<MLP_H3>(), "layer 3's chunk is the largest");
+    hipError_t e = gemm_b3 ? launch_kernel<mlp_grad_w_b3_kernel>(first, GW_THREADS, b3_bytes, stream, T, (long)n)
+                           : launch_kernel<mlp_grad_w_kernel>(first, GW_THREADS, lds_bytes, stream, T, (long)n);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(mlp_grad_reduce_kernel<4>, dim3(RED_BLOCKS), dim3(64 * RED_WAVES), 0,
                        (hipStream_t)stream, T, grad_out, norm_mask, norm_ws, norm_step, err);
@@ -588,27 +505,11 @@ extern "C" int flyhip_mlp_reduce_blocks(void) { return RED_BLOCKS; }
 static int g_fused_grid_override = 0;    // test / tuning hook: fewer workgroups than CUs (each then walks more tiles)
 extern "C" void flyhip_debug_set_fused_grid(int grid) { g_fused_grid_override = grid; }
 extern "C" int flyhip_debug_get_fused_grid(void) { return g_fused_grid_override; }
-static int fused_cus()
-{
-    static int cus[16] = {0};        // per DEVICE: a process may drive more than one
-    int dev = 0;
-    hipDeviceProp_t pr;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 256;
-    if (!cus[dev]) cus[dev] = hipGetDeviceProperties(&pr, dev) == hipSuccess ? pr.multiProcessorCount : 256;
-    return cus[dev];
-}
-static int fused_grid(int64_t n)
-{
-    int g = fused_cus();
-    if (g_fused_grid_override > 0 && g_fused_grid_override < g) g = g_fused_grid_override;
-    const long tiles = (n + BM - 1) / BM;
-    return (int)(tiles < g ? tiles : g);
-}
 
 extern "C" int64_t flyhip_mlp_fused_workspace_floats(void)
 {
     // one partial slab per workgroup; chunked layout: every layer's block padded to whole 1 KiB chunks
-    return (int64_t)fused_cus() * (fs_pad256(FS_STRIDE1) + fs_pad256(FS_STRIDE2) + fs_pad256(FS_STRIDE3) + fs_pad256(FS_STRIDE4));
+    return (int64_t)device_cus() * (fs_pad256(FS_STRIDE1) + fs_pad256(FS_STRIDE2) + fs_pad256(FS_STRIDE3) + fs_pad256(FS_STRIDE4));
 }
 
 extern "C" hipError_t flyhip_launch_mlp_fused_grad(const float* P, const uint16_t* PB, const uint16_t* PTB, const float* x,
@@ -617,38 +518,22 @@ extern "C" hipError_t flyhip_launch_mlp_fused_grad(const float* P, const uint16_
                                                    float* workspace, float* grad_out, const float* norm_mask, float* norm_ws,
                                                    int* norm_step, float* loss_part, float* const* dump, void* stream)
 {
-    const int grid = fused_grid(n);
-    FusedDump d = {};
-    // debug_dump: 8 pointers = the chain dump (tests); ONE pointer followed by NULL = a stamp buffer (tools/stamp_fused.py)
-    const int mode = dump == nullptr ? 0 : (dump[1] == nullptr ? 2 : 1);
-    if (mode == 1) { d.out = dump[0]; d.h1 = dump[1]; d.h2 = dump[2]; d.h3 = dump[3]; d.dz4 = dump[4]; d.dz3 = dump[5]; d.dz2 = dump[6]; d.dz1 = dump[7]; }
-    if (mode == 2) d.out = dump[0];
-    const void* fn = mode == 0 ? reinterpret_cast<const void*>(mlp_fused_step_kernel<0>)
-                   : mode == 1 ? reinterpret_cast<const void*>(mlp_fused_step_kernel<1>)
-                               : reinterpret_cast<const void*>(mlp_fused_step_kernel<2>);
-    {           // (per launch: the attribute belongs to the CURRENT device)
-        hipError_t ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, FS_LDS_BYTES);
-        if (ea != hipSuccess) return ea;
-    }
-#define FS_LAUNCH(M_)                                                                                                             \
-    hipLaunchKernelGGL(mlp_fused_step_kernel<M_>, dim3(grid), dim3(THREADS), FS_LDS_BYTES, (hipStream_t)stream, P, PB, PTB, x,     \
-                       (long)n, action, old_logp, adv, target, var, inv_batch, clip, workspace, loss_part, d)
-    if (mode == 0) FS_LAUNCH(0); else if (mode == 1) FS_LAUNCH(1); else FS_LAUNCH(2);
-#undef FS_LAUNCH
-    hipError_t e = hipGetLastError();
+    const int grid = fused_grid(n, BM);
+    FusedDump d;
+    hipError_t e = with_int<0, 1, 2>(decode_dump(dump, d), [&](auto mode) {
+        return launch_kernel<mlp_fused_step_kernel<mode.value>>(grid, THREADS, FS_LDS_BYTES, stream, P, PB, PTB, x, (long)n, action, old_logp,
+                                                                adv, target, var, inv_batch, clip, workspace, loss_part, d);
+    });
     if (e != hipSuccess) return e;
     // the slabs have the layout the reduction already sums: per layer `grid` blocks of N*KP + N floats, padded to whole 1 KiB chunks
     // and interleaved chunk by chunk (fs_slab)
     GradWTable T;
     const int N[4] = {MLP_H1, MLP_H2, MLP_H3, MLP_OUT};
     const int KP[4] = {MLP_IN_PAD, MLP_H1, MLP_H2, MLP_H3};
+    float* part[4];
     float* w = workspace;
-    for (int l = 0; l < 4; ++l) {
-        T.l[l].dz = nullptr; T.l[l].a = nullptr; T.l[l].partial = w;
-        T.l[l].N = N[l]; T.l[l].Ka = KP[l]; T.l[l].KP = KP[l]; T.l[l].wgs = grid; T.l[l].first_block = 0; T.l[l].accumulate = 0;
-        T.l[l].chunked = 1;
-        w += (long)grid * fs_pad256((long)N[l] * KP[l] + N[l]);
-    }
+    for (int l = 0; l < 4; ++l) { part[l] = w; w += (long)grid * fs_pad256((long)N[l] * KP[l] + N[l]); }
+    fill_slab_table(T, N, KP, part, grid, 1);
     // (loads in flight per wave: 4 -> 15.8 us for the 256 slabs, 8 -> 17.2, 16 -> 58 (the 1024-thread block's register budget))
     hipLaunchKernelGGL(mlp_grad_reduce_kernel<4>, dim3(RED_BLOCKS), dim3(64 * RED_WAVES), 0, (hipStream_t)stream, T, grad_out,
                        norm_mask, norm_ws, norm_step, (const int*)nullptr);

@@ -10,6 +10,7 @@
 #include <stdint.h>
 #include "flyhip.h"
 #include "obs_norm.h"
+#include "launch.h"
 
 namespace {
 

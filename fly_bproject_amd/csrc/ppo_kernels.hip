@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "flyhip.h"
+#include "launch.h"
 
 namespace {
 
@@ -309,27 +310,17 @@ extern "C" hipError_t flyhip_launch_td_gae(const float* reward, const float* v, 
                                            float* target_out, float* adv_out, int mode, void* stream)
 {
     const float gl = (float)((double)gamma * (double)lambda);   // python double product, ppo.py:167
-    if (mode & PPO_GAE_SCAN) {
-        if (mode & PPO_GAE_DONE_PER_STEP)
-            hipLaunchKernelGGL((ppo_td_gae_scan_kernel<1>), dim3((unsigned)N), dim3(64), 0, (hipStream_t)stream, reward, v,
-                               v_next, done, gamma, gl, (long)T, (long)N, target_out, adv_out);
-        else
-            hipLaunchKernelGGL((ppo_td_gae_scan_kernel<0>), dim3((unsigned)N), dim3(64), 0, (hipStream_t)stream, reward, v,
-                               v_next, done, gamma, gl, (long)T, (long)N, target_out, adv_out);
-        return hipGetLastError();
-    }
+    if (mode & PPO_GAE_SCAN)
+        return with_int<0, 1>(mode & PPO_GAE_DONE_PER_STEP ? 1 : 0, [&](auto m) {
+            return launch_kernel<ppo_td_gae_scan_kernel<m.value>>(dim3((unsigned)N), 64, 0, stream, reward, v, v_next, done, gamma, gl,
+                                                                  (long)T, (long)N, target_out, adv_out);
+        });
     int block = 64;                                              // one wave per workgroup: spread envs over CUs
     int grid = (int)((N + block - 1) / block);
-#define GAE(M) hipLaunchKernelGGL((ppo_td_gae_kernel<M>), dim3(grid), dim3(block), 0, (hipStream_t)stream, \
-                                  reward, v, v_next, done, gamma, gl, (long)T, (long)N, target_out, adv_out)
-    switch (mode & 3) {
-    case 0: GAE(0); break;
-    case 1: GAE(1); break;
-    case 2: GAE(2); break;
-    default: GAE(3); break;
-    }
-#undef GAE
-    return hipGetLastError();
+    return with_int<0, 1, 2, 3>(mode & 3, [&](auto m) {
+        return launch_kernel<ppo_td_gae_kernel<m.value>>(grid, block, 0, stream, reward, v, v_next, done, gamma, gl, (long)T, (long)N,
+                                                         target_out, adv_out);
+    });
 }
 
 extern "C" hipError_t flyhip_launch_adv_stats(const float* adv, int64_t n, float* stats, void* stream)

@@ -12,6 +12,7 @@
 #include <stdint.h>
 #include "flyhip.h"
 #include "value_norm.h"
+#include "launch.h"
 
 namespace {
 
@@ -184,21 +185,15 @@ extern "C" hipError_t flyhip_launch_td_gae_vnorm(const float* reward, const floa
 {
     const float gl = (float)((double)gamma * (double)lambda);   // python double product, ppo.py:167
     // always FLY_VALUE_NORM_SETS workgroups: one set each, and those with no env write an empty set
-#define VGAE(K, M) hipLaunchKernelGGL((K<M>), dim3(VALUE_NORM_SETS), dim3(GAE_BLOCK), 0, (hipStream_t)stream, reward, v, \
-                                      v_next, done, table, gamma, gl, (long)T, (long)N, target_out, adv_out, sets)
-    if (mode & PPO_GAE_SCAN) {
-        if (mode & PPO_GAE_DONE_PER_STEP) VGAE(value_td_gae_scan_kernel, 1);
-        else VGAE(value_td_gae_scan_kernel, 0);
-        return hipGetLastError();
-    }
-    switch (mode & 3) {
-    case 0: VGAE(value_td_gae_kernel, 0); break;
-    case 1: VGAE(value_td_gae_kernel, 1); break;
-    case 2: VGAE(value_td_gae_kernel, 2); break;
-    default: VGAE(value_td_gae_kernel, 3); break;
-    }
-#undef VGAE
-    return hipGetLastError();
+    if (mode & PPO_GAE_SCAN)
+        return with_int<0, 1>(mode & PPO_GAE_DONE_PER_STEP ? 1 : 0, [&](auto m) {
+            return launch_kernel<value_td_gae_scan_kernel<m.value>>(VALUE_NORM_SETS, GAE_BLOCK, 0, stream, reward, v, v_next, done, table,
+                                                                    gamma, gl, (long)T, (long)N, target_out, adv_out, sets);
+        });
+    return with_int<0, 1, 2, 3>(mode & 3, [&](auto m) {
+        return launch_kernel<value_td_gae_kernel<m.value>>(VALUE_NORM_SETS, GAE_BLOCK, 0, stream, reward, v, v_next, done, table, gamma,
+                                                           gl, (long)T, (long)N, target_out, adv_out, sets);
+    });
 }
 
 extern "C" hipError_t flyhip_launch_value_norm_merge(const double* stats_in, const double* sets, int64_t k, double* stats_out,

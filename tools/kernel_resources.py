@@ -2,12 +2,18 @@
 """Per-kernel register / LDS / scratch figures of the gfx950 code objects inside the built objects (no GPU needed):
 
     python tools/kernel_resources.py [csv-out]
+    python tools/kernel_resources.py --isa-digest [csrc-dir] > digest.txt
+
+--isa-digest: one line per kernel, sorted by name -- file, kernel, the figures above, and a SHA-256 of the kernel's disassembled
+body (llvm-objdump -d, addresses and comments stripped) -- so that the device code of two builds (say, before and after a change
+that touches host code only) is compared with `diff`: the order kernels are emitted in does not matter, anything else shows.
 
 For every csrc/*.o: the .hip_fatbin section is unbundled (clang-offload-bundler) and the AMDGPU metadata note of the code
 object read (llvm-readelf --notes): .vgpr_count, .agpr_count, .sgpr_count, .vgpr_spill_count, .sgpr_spill_count,
 .private_segment_fixed_size (scratch bytes per lane), .group_segment_fixed_size (static LDS).  What profiles/README.md quotes.
 """
 import glob
+import hashlib
 import os
 import re
 import subprocess
@@ -31,7 +37,25 @@ def short(n):
     return m.group(1) if m else n[:80]
 
 
-def kernels_of(obj):
+def bodies_of(co):
+    """symbol -> its instructions, without addresses, encodings and comments, and without the padding behind its last
+    instruction (s_nop / s_code_end / elided zeros up to the next symbol or the end of the section: that depends on the kernel's neighbours)"""
+    dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", co], capture_output=True, text=True,
+                         check=True).stdout
+    out, cur = {}, None
+    for line in dis.splitlines():
+        m = re.match(r"[0-9a-f]+ <(.+)>:$", line)
+        if m:
+            cur = out.setdefault(m.group(1), [])
+        elif cur is not None and line.strip():
+            cur.append(re.sub(r"\s+", " ", line.split("//")[0]).strip())
+    for body in out.values():
+        while body and body[-1] in ("s_nop 0", "s_code_end", "..."):
+            body.pop()
+    return out
+
+
+def kernels_of(obj, isa=False):
     with tempfile.TemporaryDirectory() as d:
         fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "k.co")
         subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fat])
@@ -40,6 +64,7 @@ def kernels_of(obj):
         subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--type=o", "--input=" + fat,
                                "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co, "--unbundle"])
         notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True).stdout
+        bodies = bodies_of(co) if isa else {}
     ks, cur = [], None
     for line in notes.splitlines():
         m = re.match(r"\s*-?\s*(\.[a-z_]+):\s*(.*)$", line)
@@ -54,10 +79,22 @@ def kernels_of(obj):
     ks = [k for k in ks if ".name" in k]
     for k, dn in zip(ks, demangle([k[".name"] for k in ks])):
         k["kernel"] = short(dn)
+        if isa:
+            k["isa"] = hashlib.sha256("\n".join(bodies[k[".name"]]).encode()).hexdigest()
     return ks
 
 
+def isa_digest(csrc):
+    lines = []
+    for obj in sorted(glob.glob(os.path.join(csrc, "*.o"))):
+        for k in kernels_of(obj, isa=True):
+            lines.append(" ".join([os.path.basename(obj)[:-2], k["kernel"].replace(" ", "")] + [str(k.get(x, "")) for x in KEYS] + [k["isa"]]))
+    sys.stdout.write("\n".join(sorted(lines)) + "\n")
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--isa-digest":
+        return isa_digest(sys.argv[2] if len(sys.argv) > 2 else os.path.join(REPO, "fly_bproject_amd", "csrc"))
     rows = []
     for obj in sorted(glob.glob(os.path.join(REPO, "fly_bproject_amd", "csrc", "*.o"))):
         for k in kernels_of(obj):
