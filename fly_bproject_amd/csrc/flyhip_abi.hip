@@ -351,6 +351,7 @@ int ppo_td_gae(const float* reward, const float* v, const float* v_next, const f
 int ppo_adv_stats(const float* adv, int64_t n, float* stats, void* stream)
 {
     if (!adv || !stats || n <= 1) return fail(FLY_E_ARG, "ppo_adv_stats: bad argument");
+    if (reinterpret_cast<uintptr_t>(stats) & 7) return fail(FLY_E_ARG, "ppo_adv_stats: stats is not 8-byte aligned");
     hipError_t e = flyhip_launch_adv_stats(adv, n, stats, stream);
     if (e != hipSuccess) return hip_fail(e, "ppo_adv_stats launch");
     return FLY_OK;

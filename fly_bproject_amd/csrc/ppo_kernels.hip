@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "flyhip.h"
+#include "value_norm.h"
 #include "launch.h"
 
 namespace {
@@ -148,49 +149,60 @@ __global__ __launch_bounds__(64) void ppo_td_gae_scan_kernel(
 }
 
 // Advantage normalisation (named by BASELINE's north_star; the reference does NOT normalise,
-// ppo.py:171, so this is opt-in): per-block partial sums of x and x^2, then (x - mean) / (std + eps)
-// with the unbiased std torch uses.  Two launches; `stats` [2 + 2*blocks] is scratch, stats[0..1]
-// return mean and std.  With data-parallel ranks the caller all-reduces the two partial totals.
-__global__ __launch_bounds__(256) void ppo_adv_stats_kernel(const float* __restrict__ adv, long n,
-                                                            float* __restrict__ part)
+// ppo.py:171, so this is opt-in): (x - mean) / (std + eps) with the unbiased std torch uses.  The statistics are CENTRED
+// second moments in float64 -- raw sums of x and x^2 in fp32 lose the variance to cancellation once |mean| is a few dozen
+// std.  Every thread keeps Welford moments (count, mean, M2) of its grid-stride elements, a fixed
+// shuffle / LDS tree merges them per workgroup (Chan et al.'s update, value_norm.h) and one workgroup merges the
+// ADV_BLOCKS sets in index order: deterministic.  stats[0..1] return sum = count * mean and M2 = sum (x - mean)^2, each
+// rounded once to fp32; stats + 2 is the scratch of the per-workgroup sets (f64 mean | M2; a workgroup's count follows
+// from n).  Data-parallel callers combine the ranks' (sum, M2) pairs (ppo.py: combine_adv_stats).
+constexpr int ADV_BLOCKS = 128;         // 128 sets x 2 doubles = the 512 floats behind stats[0..1]
+
+__device__ __forceinline__ long adv_block_count(long n, int b)
 {
-    __shared__ float red[2][4];
-    float s = 0.0f, ss = 0.0f;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const float x = adv[i];
-        s += x; ss += x * x;
+    const long round = (long)ADV_BLOCKS * 256;
+    const long rem = n % round - (long)b * 256;
+    return n / round * 256 + (rem < 0 ? 0 : rem > 256 ? 256 : rem);
+}
+
+__global__ __launch_bounds__(256) void ppo_adv_stats_kernel(const float* __restrict__ adv, long n,
+                                                            double* __restrict__ part)
+{
+    __shared__ double red[3][4];
+    double cn = 0.0, cm = 0.0, cq = 0.0;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
+        value_moments_add(cn, cm, cq, adv[i]);
+    for (int o = 32; o > 0; o >>= 1) {
+        const double nb = __shfl_down(cn, o, 64), mb = __shfl_down(cm, o, 64), qb = __shfl_down(cq, o, 64);
+        value_moments_merge(cn, cm, cq, nb, mb, qb);
     }
-    for (int o = 32; o > 0; o >>= 1) { s += __shfl_down(s, o, 64); ss += __shfl_down(ss, o, 64); }
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s; red[1][threadIdx.x >> 6] = ss; }
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = cn; red[1][threadIdx.x >> 6] = cm; red[2][threadIdx.x >> 6] = cq; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        part[2 * blockIdx.x] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-        part[2 * blockIdx.x + 1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+        for (int w = 1; w < 4; ++w) value_moments_merge(cn, cm, cq, red[0][w], red[1][w], red[2][w]);
+        part[2 * blockIdx.x] = cm;
+        part[2 * blockIdx.x + 1] = cq;
     }
 }
 
 __global__ __launch_bounds__(256) void ppo_adv_apply_kernel(float* __restrict__ adv, long n, const float* __restrict__ totals,
                                                             float count, float eps)
 {
-    const float mean = totals[0] / count;
-    const float var = fmaxf((totals[1] - count * mean * mean) / (count - 1.0f), 0.0f);
-    const float inv = 1.0f / (sqrtf(var) + eps);
+    const double mean = (double)totals[0] / (double)count;
+    const double var = fmax((double)totals[1] / ((double)count - 1.0), 0.0);
+    const double inv = 1.0 / (sqrt(var) + (double)eps);
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
-        adv[i] = (adv[i] - mean) * inv;
+        adv[i] = (float)(((double)adv[i] - mean) * inv);
 }
 
-__global__ __launch_bounds__(256) void ppo_adv_totals_kernel(const float* __restrict__ part, int blocks, float* __restrict__ totals)
+__global__ __launch_bounds__(64) void ppo_adv_totals_kernel(const double* __restrict__ part, long n, float* __restrict__ totals)
 {
-    __shared__ float red[2][4];
-    float s = 0.0f, ss = 0.0f;
-    for (int b = threadIdx.x; b < blocks; b += 256) { s += part[2 * b]; ss += part[2 * b + 1]; }
-    for (int o = 32; o > 0; o >>= 1) { s += __shfl_down(s, o, 64); ss += __shfl_down(ss, o, 64); }
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s; red[1][threadIdx.x >> 6] = ss; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        totals[0] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-        totals[1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-    }
+    if (threadIdx.x != 0) return;
+    double cn = 0.0, cm = 0.0, cq = 0.0;
+    for (int b = 0; b < ADV_BLOCKS; ++b)
+        value_moments_merge(cn, cm, cq, (double)adv_block_count(n, b), part[2 * b], part[2 * b + 1]);
+    totals[0] = (float)(cn * cm);
+    totals[1] = (float)(cq > 0.0 ? cq : 0.0);
 }
 
 // ppo.py:233 + :237 in one tiny launch: score += mean(reward)/num_eval_freq (kept on the device:
@@ -325,11 +337,11 @@ extern "C" hipError_t flyhip_launch_td_gae(const float* reward, const float* v, 
 
 extern "C" hipError_t flyhip_launch_adv_stats(const float* adv, int64_t n, float* stats, void* stream)
 {
-    const int blocks = 256;
-    hipLaunchKernelGGL(ppo_adv_stats_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, adv, (long)n, stats + 2);
+    double* part = reinterpret_cast<double*>(stats + 2);         // the ABI checks that stats is 8-byte aligned
+    hipLaunchKernelGGL(ppo_adv_stats_kernel, dim3(ADV_BLOCKS), dim3(256), 0, (hipStream_t)stream, adv, (long)n, part);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(ppo_adv_totals_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, stats + 2, blocks, stats);
+    hipLaunchKernelGGL(ppo_adv_totals_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, part, (long)n, stats);
     return hipGetLastError();
 }
 

@@ -121,6 +121,17 @@ def normalize_obs_ref(x, table):
     return ((x - table[:k]) * table[k:2 * k]).clamp(-clip, clip)
 
 
+def combine_adv_stats(ranks, count):
+    """The all-rank (sum, M2) of the advantages from every rank's ppo_adv_stats pair: `ranks` [world][2] holds
+    (sum_r, M2_r) over `count` elements each, M2 the centred second moment.  M2 = sum_r M2_r + count (mean_r - mean)^2
+    (Chan et al.'s update for equal counts), in float64 on the device, rounded once: what ppo_adv_apply takes as totals."""
+    r = ranks.to(torch.float64)
+    total = r[:, 0].sum()
+    mean = total / (count * r.shape[0])
+    m2 = r[:, 1].sum() + count * ((r[:, 0] / count - mean) ** 2).sum()
+    return torch.stack((total, m2)).to(torch.float32)
+
+
 class PPO:
     def __init__(self, args, env=None):
         self.args = args
@@ -499,7 +510,10 @@ class PPO:
         _lib.check(self._lib.ppo_adv_stats(p(self.all_advantage), C.c_int64(cnt), p(self._adv_stats), _lib.stream_ptr()),
                    "ppo_adv_stats")
         if self.world_size > 1:
-            dist.all_reduce(self._adv_stats[:2], op=dist.ReduceOp.SUM)
+            mine = self._adv_stats[:2].clone()
+            parts = [torch.empty_like(mine) for _ in range(self.world_size)]
+            dist.all_gather(parts, mine)                            # every rank combines the same pairs in rank order
+            self._adv_stats[:2].copy_(combine_adv_stats(torch.stack(parts), cnt))
         _lib.check(self._lib.ppo_adv_apply(p(self.all_advantage), C.c_int64(cnt), p(self._adv_stats),
                                            C.c_float(float(cnt * self.world_size)), C.c_float(1e-8), _lib.stream_ptr()),
                    "ppo_adv_apply")

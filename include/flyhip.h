@@ -185,10 +185,13 @@ int ppo_td_gae(const float* reward, const float* v, const float* v_next, const f
                float* target_out, float* adv_out, int mode_flags, void* stream);
 
 /* Advantage normalisation (opt-in; the reference uses raw advantages, ppo.py:171).
- *   ppo_adv_stats: stats[0] = sum(adv), stats[1] = sum(adv^2) over n elements (stats: >= 514 floats).
- *   ppo_adv_apply: adv = (adv - mean) / (std + eps) with mean/std from totals[0..1] over `count`
- *   elements (unbiased std, as torch.std).  Data-parallel callers all-reduce stats[0..1] and pass
- *   the global count. */
+ *   ppo_adv_stats: stats[0] = sum(adv), stats[1] = M2 = sum((adv - mean)^2) over n elements, the CENTRED second moment,
+ *   both accumulated in float64 (per-thread Welford moments merged in a fixed order) and rounded once to fp32
+ *   (stats: >= 514 floats, 8-byte aligned; stats[2..] is scratch).
+ *   ppo_adv_apply: adv = (adv - mean) / (std + eps) with mean = totals[0] / count and std = sqrt(totals[1] / (count - 1))
+ *   (unbiased, as torch.std), evaluated in float64 and rounded once.  Data-parallel callers gather every rank's
+ *   stats[0..1], combine them into the all-rank (sum, M2) -- M2 = sum_r M2_r + n_r (mean_r - mean)^2 -- and pass the
+ *   global count.  With var = 0 (constant input) the output is rounding noise times 1 / eps. */
 int ppo_adv_stats(const float* adv, int64_t n, float* stats, void* stream);
 int ppo_adv_apply(float* adv, int64_t n, const float* totals, float count, float eps, void* stream);
 

@@ -320,28 +320,30 @@ def test_reference_default_env_count():
 
 def test_rollout_bookkeeping_equals_per_step_calls():
     """ppo_rollout_bookkeeping over a block of rows == ppo_step_bookkeeping row by row, bit for bit
-    (score terms added in row order, variance decayed once per row, clamp included)."""
+    (score terms added in row order, variance decayed once per row, clamp included) -- also at env counts
+    that are no multiple of 4, where every other row starts off a 16-byte boundary, and below one float4."""
     import ctypes as C
     from fly_bproject_amd import _lib
     lib = _lib.load()
     torch.manual_seed(5)
-    rows, n = 37, 8192
-    reward = torch.randn(rows, n, device="cuda:0")
     p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
-    for dec, v0 in ((1e-5, 0.2), (1e-3, 0.02), (0.0, 0.2)):
-        s1 = torch.full((), 0.25, device="cuda:0"); v1 = torch.full((18,), v0, device="cuda:0")
-        for r in range(rows):
-            _lib.check(lib.ppo_step_bookkeeping(p(reward[r]), n, p(s1), C.c_float(0.01), p(v1), 18, C.c_float(dec),
-                                                C.c_float(0.01), None), "step")
-        s2 = torch.full((), 0.25, device="cuda:0"); v2 = torch.full((18,), v0, device="cuda:0")
-        terms = torch.zeros(rows, device="cuda:0")
-        applied = torch.full((1,), 5, dtype=torch.int32, device="cuda:0")
-        _lib.check(lib.ppo_rollout_bookkeeping(p(reward), rows, n, p(terms), p(s2), C.c_float(0.01), p(v2), 18,
-                                               C.c_float(dec), C.c_float(0.01), p(applied), None), "rollout")
-        torch.cuda.synchronize()
-        assert torch.equal(s1, s2) and torch.equal(v1, v2)
-        assert int(applied) == 5 + rows                      # the word the policy launches subtract from their row index
-    assert float(v2[0]) == float(np.float32(0.2))            # dec = 0: untouched
+    for n in (8192, 4099, 5):
+        rows = 37
+        reward = torch.randn(rows, n, device="cuda:0")
+        for dec, v0 in ((1e-5, 0.2), (1e-3, 0.02), (0.0, 0.2)):
+            s1 = torch.full((), 0.25, device="cuda:0"); v1 = torch.full((18,), v0, device="cuda:0")
+            for r in range(rows):
+                _lib.check(lib.ppo_step_bookkeeping(p(reward[r]), n, p(s1), C.c_float(0.01), p(v1), 18, C.c_float(dec),
+                                                    C.c_float(0.01), None), "step")
+            s2 = torch.full((), 0.25, device="cuda:0"); v2 = torch.full((18,), v0, device="cuda:0")
+            terms = torch.zeros(rows, device="cuda:0")
+            applied = torch.full((1,), 5, dtype=torch.int32, device="cuda:0")
+            _lib.check(lib.ppo_rollout_bookkeeping(p(reward), rows, n, p(terms), p(s2), C.c_float(0.01), p(v2), 18,
+                                                   C.c_float(dec), C.c_float(0.01), p(applied), None), "rollout")
+            torch.cuda.synchronize()
+            assert torch.equal(s1, s2) and torch.equal(v1, v2)
+            assert int(applied) == 5 + rows                      # the word the policy launches subtract from their row index
+        assert float(v2[0]) == float(np.float32(0.2))            # dec = 0: untouched
 
 
 @pytest.mark.parametrize("n", [33, 8192])
