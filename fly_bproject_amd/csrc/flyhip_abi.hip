@@ -292,6 +292,47 @@ int ppo_value_norm_apply(const float* target, int64_t n, const float* table, flo
     return FLY_OK;
 }
 
+// the checks the two episodic entry points share; `what` names the caller in the message
+static int check_episodic(const char* what, bool any_null, int64_t max_episode_length, int64_t T, int64_t N, int mode_flags)
+{
+    if (any_null) return fail(FLY_E_ARG, "%s: null pointer", what);
+    if (T <= 0 || N <= 0) return fail(FLY_E_ARG, "%s: T and N must be > 0", what);
+    if (max_episode_length <= 0) return fail(FLY_E_ARG, "%s: max_episode_length must be > 0", what);
+    if (mode_flags != 0 && mode_flags != PPO_GAE_SCAN)
+        return fail(FLY_E_ARG, "%s: mode_flags must be 0 or PPO_GAE_SCAN (got %d)", what, mode_flags);
+    return FLY_OK;
+}
+
+int ppo_td_gae_episodic(const float* reward, const float* v, const float* v_next, const int64_t* reset, const int64_t* progress,
+                        const int64_t* ended_prev, int64_t max_episode_length, float gamma, float lambda, int64_t T, int64_t N,
+                        float* target_out, float* adv_out, int mode_flags, void* stream)
+{
+    int rc = check_episodic("ppo_td_gae_episodic",
+                            !reward || !v || !v_next || !reset || !progress || !ended_prev || !target_out || !adv_out,
+                            max_episode_length, T, N, mode_flags);
+    if (rc) return rc;
+    hipError_t e = flyhip_launch_td_gae_episodic(reward, v, v_next, reset, progress, ended_prev, max_episode_length, gamma, lambda,
+                                                 T, N, target_out, adv_out, mode_flags, stream);
+    if (e != hipSuccess) return hip_fail(e, "ppo_td_gae_episodic launch");
+    return FLY_OK;
+}
+
+int ppo_td_gae_episodic_vnorm(const float* reward, const float* v, const float* v_next, const int64_t* reset,
+                              const int64_t* progress, const int64_t* ended_prev, int64_t max_episode_length, const float* table,
+                              float gamma, float lambda, int64_t T, int64_t N, float* target_out, float* adv_out, double* sets,
+                              int mode_flags, void* stream)
+{
+    int rc = check_episodic("ppo_td_gae_episodic_vnorm",
+                            !reward || !v || !v_next || !reset || !progress || !ended_prev || !table || !target_out || !adv_out || !sets,
+                            max_episode_length, T, N, mode_flags);
+    if (rc) return rc;
+    if (reinterpret_cast<uintptr_t>(sets) & 7) return fail(FLY_E_ARG, "ppo_td_gae_episodic_vnorm: sets is not 8-byte aligned");
+    hipError_t e = flyhip_launch_td_gae_episodic_vnorm(reward, v, v_next, reset, progress, ended_prev, max_episode_length, table,
+                                                       gamma, lambda, T, N, target_out, adv_out, sets, mode_flags, stream);
+    if (e != hipSuccess) return hip_fail(e, "ppo_td_gae_episodic_vnorm launch");
+    return FLY_OK;
+}
+
 int fly_render(FlyHandle h, const float* poses, int32_t frames, const FlyRenderConfig* rc, uint32_t* rgba_out,
                uint8_t* id_out, void* stream)
 {

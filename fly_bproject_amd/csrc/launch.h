@@ -51,6 +51,16 @@ hipError_t flyhip_launch_value_norm_merge(const double* stats_in, const double* 
                                           float* table_out, void* stream);
 hipError_t flyhip_launch_value_norm_apply(const float* target, int64_t n, const float* table, float* out, void* stream);
 
+// gae_episodic.hip
+hipError_t flyhip_launch_td_gae_episodic(const float* reward, const float* v, const float* v_next, const int64_t* reset,
+                                         const int64_t* progress, const int64_t* ended_prev, int64_t max_episode_length,
+                                         float gamma, float lambda, int64_t T, int64_t N, float* target_out, float* adv_out,
+                                         int mode, void* stream);
+hipError_t flyhip_launch_td_gae_episodic_vnorm(const float* reward, const float* v, const float* v_next, const int64_t* reset,
+                                               const int64_t* progress, const int64_t* ended_prev, int64_t max_episode_length,
+                                               const float* table, float gamma, float lambda, int64_t T, int64_t N,
+                                               float* target_out, float* adv_out, double* sets, int mode, void* stream);
+
 // mlp_mfma.hip
 hipError_t flyhip_launch_mlp_forward(const float* P, const float* PF, const float* x, int64_t n, float* mu_out, float* v_out,
                                      float* out_save, float* h1_save, float* h2_save, float* h3_save, const uint16_t* PB,

@@ -45,6 +45,21 @@ __device__ __forceinline__ void value_moments_merge(double& n, double& mean, dou
     m2 += qb + d * d * (n * nb * inv);
     n = t;
 }
+
+// The wave's 64 per-lane moments -> lane 0, by a fixed shuffle tree; lane 0 writes the workgroup's set.
+__device__ __forceinline__ void value_write_set(double n, double mean, double m2, double* __restrict__ set)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double nb = __shfl_down(n, o, 64), mb = __shfl_down(mean, o, 64), qb = __shfl_down(m2, o, 64);
+        value_moments_merge(n, mean, m2, nb, mb, qb);
+    }
+    if (threadIdx.x == 0) {
+        set[0] = n;
+        set[1] = mean;
+        set[2] = m2 > 0.0 ? m2 : 0.0;
+    }
+}
 #endif
 
 #endif

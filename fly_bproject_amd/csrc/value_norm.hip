@@ -20,21 +20,6 @@ constexpr int GAE_BLOCK = 64;               // one wave per workgroup, as ppo_td
 constexpr int MERGE_THREADS = 256;          // sets staged per round of the merge
 constexpr int APPLY_THREADS = 256;
 
-// The wave's 64 per-lane moments -> lane 0, by a fixed shuffle tree; lane 0 writes the workgroup's set.
-__device__ __forceinline__ void value_write_set(double n, double mean, double m2, double* __restrict__ set)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double nb = __shfl_down(n, o, 64), mb = __shfl_down(mean, o, 64), qb = __shfl_down(m2, o, 64);
-        value_moments_merge(n, mean, m2, nb, mb, qb);
-    }
-    if (threadIdx.x == 0) {
-        set[0] = n;
-        set[1] = mean;
-        set[2] = m2 > 0.0 ? m2 : 0.0;
-    }
-}
-
 // lane = env, t walks backwards: the loop of ppo_td_gae_kernel, per element the same ops in the same order, with v and v_next
 // replaced by their denormalised values.  Workgroup g takes the env blocks g, g + gridDim.x, ... (one block for N <= 16384), and
 // every lane keeps Welford moments of the targets it wrote -- not raw sums: targets of mean 1e3 / std 1e-2 keep their digits.

@@ -135,6 +135,9 @@ def combine_adv_stats(ranks, count):
 class PPO:
     def __init__(self, args, env=None):
         self.args = args
+        self.gae = getattr(args, "gae", "reference")                # read first: a bad value must not leave an env behind
+        if self.gae not in ("reference", "episodic"):
+            raise ValueError("gae must be reference or episodic (got %r)" % (self.gae,))
         self.env = env if env is not None else Fly(args)           # ppo.py:110
         self.num_acts = self.env.num_act
         self.num_obs = self.env.num_obs
@@ -185,6 +188,9 @@ class PPO:
         # opt-in (`normalize_value`, rl_games' normalize_value): the critic regresses on TD targets kept at zero mean / unit
         # variance by running statistics, and make_data maps its outputs back to reward units
         self.normalize_value = bool(getattr(args, "normalize_value", False))
+        # opt-in (`gae="episodic"`): per-step end flags, a recurrence that stops at episode ends, a bootstrap through time-outs
+        # and no training signal from the step that performs a reset.  NOT the reference's estimator (Q1/Q2).
+        # (self.gae, validated above)
         self.use_graph = bool(getattr(args, "graph", False))
         # one launch per ROLLOUT (ppo_rollout_all): each workgroup loops over the T steps of its own 32 envs.  The device then
         # runs ahead of the host's step count inside a rollout, but everything `run()` reads per step is a ROW the launch wrote
@@ -197,7 +203,11 @@ class PPO:
         if want is None:
             want = os.environ.get("FLY_PERSISTENT_ROLLOUT", "1") != "0"
         self.persistent_rollout = bool(want) and T <= 4096 and not bool(getattr(args, "graph", False))
-        self._reset_rows = self._progress_rows = None
+        self._reset_rows = self._progress_rows = self._ended_prev = None
+        if self.gae == "episodic":
+            # the end flags the env carries into the first rollout: its initial reset_buf (every env resets in its first step)
+            self._flag_rows()
+            self._ended_prev = self.env.reset_buf.clone()
         self._graphs = {}
         self._graphs_form = getattr(self.env, "launch_form", 0)     # the env's kernel selection the captured graphs hold
         self._fwd_args = None
@@ -383,15 +393,23 @@ class PPO:
 
     def _td_gae_vnorm(self, values, done_f, mode):
         """make_data's GAE pass with value normalisation: raw targets and advantages under the COMMITTED table plus the targets'
-        moments (ppo_td_gae_vnorm), S_v with them folded in and its table into the scratch pair (ppo_value_norm_merge; all
-        ranks' sets in rank order), and the targets normalised under the scratch table (ppo_value_norm_apply).  Nothing
-        committed is written, so it is idempotent on a finished rollout."""
+        moments (ppo_td_gae_vnorm; with gae='episodic' ppo_td_gae_episodic_vnorm, which reads the flag rows, not `done_f`), S_v
+        with them folded in and its table into the scratch pair (ppo_value_norm_merge; all ranks' sets in rank order), and the
+        targets normalised under the scratch table (ppo_value_norm_apply).  Nothing committed is written, so it is idempotent
+        on a finished rollout."""
         T, n = self.rollout_size, int(self.args.num_envs)
         p = lambda x: C.c_void_p(x.data_ptr())   # noqa: E731
-        _lib.check(self._lib.ppo_td_gae_vnorm(
-            p(self.all_reward), p(values[:T]), p(values[1:]), p(done_f), p(self._value_table), C.c_float(self.gamma),
-            C.c_float(self.lmbda), C.c_int64(T), C.c_int64(n), p(self._target), p(self.all_advantage), p(self._value_sets),
-            C.c_int(mode), _lib.stream_ptr()), "ppo_td_gae_vnorm")
+        if self.gae == "episodic":
+            _lib.check(self._lib.ppo_td_gae_episodic_vnorm(
+                p(self.all_reward), p(values[:T]), p(values[1:]), p(self._reset_rows), p(self._progress_rows),
+                p(self._ended_prev), C.c_int64(self.env.max_episode_length), p(self._value_table), C.c_float(self.gamma),
+                C.c_float(self.lmbda), C.c_int64(T), C.c_int64(n), p(self._target), p(self.all_advantage), p(self._value_sets),
+                C.c_int(mode), _lib.stream_ptr()), "ppo_td_gae_episodic_vnorm")
+        else:
+            _lib.check(self._lib.ppo_td_gae_vnorm(
+                p(self.all_reward), p(values[:T]), p(values[1:]), p(done_f), p(self._value_table), C.c_float(self.gamma),
+                C.c_float(self.lmbda), C.c_int64(T), C.c_int64(n), p(self._target), p(self.all_advantage), p(self._value_sets),
+                C.c_int(mode), _lib.stream_ptr()), "ppo_td_gae_vnorm")
         sets = self._value_sets
         if self.world_size > 1:
             import torch.distributed as dist
@@ -422,7 +440,26 @@ class PPO:
 
     @all_done.setter
     def all_done(self, value):
+        if self.gae == "episodic":
+            raise ValueError("all_done has no meaning with gae='episodic': the estimator reads the per-step reset / progress "
+                             "rows the rollout wrote, not a done mask")
         self._all_done = value
+
+    def _flag_rows(self):
+        """The per-step [T, N] int64 rows of the env's reset / progress flags: row t holds them as step t left them."""
+        if self._reset_rows is None:
+            T, n = self.rollout_size, int(self.args.num_envs)
+            self._reset_rows = torch.zeros((T, n), dtype=torch.long, device=self.device)
+            self._progress_rows = torch.zeros((T, n), dtype=torch.long, device=self.device)
+
+    def _td_gae_episodic(self, values, mode):
+        """make_data's GAE pass with gae='episodic' (ppo_td_gae_episodic): straight from the int64 flag rows, no conversions."""
+        T, n = self.rollout_size, int(self.args.num_envs)
+        p = lambda x: C.c_void_p(x.data_ptr())   # noqa: E731
+        _lib.check(self._lib.ppo_td_gae_episodic(
+            p(self.all_reward), p(values[:T]), p(values[1:]), p(self._reset_rows), p(self._progress_rows), p(self._ended_prev),
+            C.c_int64(self.env.max_episode_length), C.c_float(self.gamma), C.c_float(self.lmbda), C.c_int64(T), C.c_int64(n),
+            p(self._target), p(self.all_advantage), C.c_int(mode), _lib.stream_ptr()), "ppo_td_gae_episodic")
 
     # ------------------------------------------------------------------------------------------
     @property
@@ -466,7 +503,8 @@ class PPO:
 
     def make_data(self):
         """ppo.py:157-171: TD target and GAE.  `all_done` is the [N,1] mask of the LAST step,
-        broadcast over T (Q1), and the recurrence never resets at episode ends (Q2)."""
+        broadcast over T (Q1), and the recurrence never resets at episode ends (Q2).  With gae='episodic' the estimator of
+        DESIGN.md 3.3d instead, from the per-step flag rows."""
         T, n = self.rollout_size, self.args.num_envs
         with torch.no_grad():
             ring = self._obs_ring
@@ -479,6 +517,18 @@ class PPO:
             else:
                 values = self.net.v(ring)                           # [T+1, N, 1]: v(obs) and v(next_obs) in one pass
             self._v_have = 0
+            if self.gae == "episodic":
+                mode = 4 if n < 512 and T >= 1024 else 0            # the same rule: PPO_GAE_SCAN for few envs x long rollout
+                if self.normalize_value:
+                    self._td_gae_vnorm(values, None, mode)
+                else:
+                    self._td_gae_episodic(values, mode)
+                self._keep = (values,)
+                if self.normalize_advantage:
+                    self._normalize_advantage()
+                obs = self._obs_norm_ring[:T] if self.normalize_obs else self.all_obs
+                target = self._target_norm if self.normalize_value else self._target
+                return obs, self.all_acts, self.all_log_prob, target, self.all_advantage
             done = self.all_done
             per_step = done.dim() == 3 and done.shape[0] == T and done.shape[1] == n
             mode = 1 if per_step else 0                             # reference path: [N,1]
@@ -785,6 +835,8 @@ class PPO:
             self._rows_applied.zero_()                              # a new rollout: no row's bookkeeping applied yet
         env.obs_buf, env.reward_buf = self._obs_rows[t + 1], self._reward_rows[t]      # ppo.py:228-229
         env._bufs.obs, env._bufs.reward = self._buf_ptrs[t]
+        if t == 0 and self.gae == "episodic":
+            self._ended_prev.copy_(env.reset_buf)                   # the flags the env carries into this rollout
         if self.fuse_rollout_step:
             # policy + sampling + env step of every 32-env tile in ONE launch (ppo.py:214-229)
             rc = lib.ppo_rollout_step(env._handle, C.byref(env._bufs), *self._step_args[t], st)
@@ -793,6 +845,10 @@ class PPO:
             rc |= lib.fly_step(env._handle, C.c_void_p(self._act_rows[t].data_ptr()), C.byref(env._bufs), st)  # ppo.py:223
         if rc:
             _lib.check(rc, "rollout step")
+        if self.gae == "episodic":
+            # row t of the flag rows, as the one-launch rollout writes them itself (captured with the step in a graph)
+            self._reset_rows[t].copy_(env.reset_buf)
+            self._progress_rows[t].copy_(env.progress_buf)
         self._after_step(t)
         if env.recorder is not None:
             env.recorder.capture(t)                                 # env 0's pose after this step (captured with it in a graph)
@@ -805,10 +861,11 @@ class PPO:
         pol, env, T = self.policy, self.env, self.rollout_size
         self._eps_all.normal_(generator=self._gen)
         self._rows_applied.zero_()
-        if self._reset_rows is None:
-            n = int(self.args.num_envs)
-            self._reset_rows = torch.zeros((T, n), dtype=torch.long, device=self.device)
-            self._progress_rows = torch.zeros((T, n), dtype=torch.long, device=self.device)
+        self._flag_rows()
+        if self.gae == "episodic":
+            # env.reset_buf is the env's own tensor before the first rollout and row T-1 of the previous rollout after it:
+            # copied before this launch overwrites that row
+            self._ended_prev.copy_(env.reset_buf)
         rec = env.recorder
         if rec is not None:
             # the launch writes env 0's pose of step t to row t of the record: frames of rows the host has not reached are

@@ -242,6 +242,35 @@ int ppo_value_norm_merge(const double* stats_in, const double* sets, int64_t k, 
                          void* stream);
 int ppo_value_norm_apply(const float* target, int64_t n, const float* table, float* out, void* stream);
 
+/* Episode-aware advantage estimate (opt-in, PPO --gae episodic).  NOT the reference's estimator
+ * (ppo.py:157-171, PPO_GAE_COMPAT): per-step end flags, a recurrence that stops at every episode end, a bootstrap through
+ * time-outs, and no training signal from the step in which the env performs its reset.  reset and progress are the int64
+ * [T][N] rows the rollout writes (row t = FlyBuffers.reset / .progress after step t), ended_prev int64 [N] the reset flags
+ * the env carried into the rollout.  Per row (t, e), in separately rounded fp32 ops in this order:
+ *     ended   = reset[t][e] != 0
+ *     timeout = ended && progress[t][e] >= max_episode_length - 1
+ *               (a fall in the very step that reaches the limit counts as a time-out: IsaacGymEnvs' convention, and the only
+ *               one these two rows allow -- they do not say why the flag was raised)
+ *     stale   = (t > 0 ? reset[t-1][e] : ended_prev[e]) != 0     the step that performed the reset
+ *     boot    = (ended && !timeout) ? 0 : 1;   cont = ended ? 0 : 1
+ *     not stale:  target = r + (gamma * v_next) * boot;  delta = target - v;  adv = (gamma lambda) * (adv_next * cont) + delta
+ *     stale:      target = v;  adv = 0   (stale takes precedence over ended; the row before it has cont = 0)
+ *   The env raises its flag after it packed the observation, so v_next at a time-out is the value of the old episode's true
+ *   next observation.  With every flag zero the outputs are ppo_td_gae's in mode PPO_GAE_DONE_PER_STEP |
+ *   PPO_GAE_MASK_RECURRENCE with done = 1, bit for bit.
+ * mode_flags: 0 (lane = env) or PPO_GAE_SCAN (one wave per env, time on lanes: the masked recurrence as a scan; a chunk that
+ *   holds an end passes on exactly nothing from beyond it; agrees with the loop to fp32 rounding).  Anything else: FLY_E_ARG.
+ * ppo_td_gae_episodic_vnorm: the same with v and v_next replaced by their values under `table` (the stale target is the
+ *   denormalised v) and the float64 moments of all T x N targets in sets, as ppo_td_gae_vnorm; under m = 0, s = 1 the
+ *   outputs are ppo_td_gae_episodic's bit for bit. */
+int ppo_td_gae_episodic(const float* reward, const float* v, const float* v_next, const int64_t* reset, const int64_t* progress,
+                        const int64_t* ended_prev, int64_t max_episode_length, float gamma, float lambda, int64_t T, int64_t N,
+                        float* target_out, float* adv_out, int mode_flags, void* stream);
+int ppo_td_gae_episodic_vnorm(const float* reward, const float* v, const float* v_next, const int64_t* reset,
+                              const int64_t* progress, const int64_t* ended_prev, int64_t max_episode_length, const float* table,
+                              float gamma, float lambda, int64_t T, int64_t N, float* target_out, float* adv_out, double* sets,
+                              int mode_flags, void* stream);
+
 /* Per-env physics domain randomisation (opt-in).  The reference has none: every env of a batch runs
  * the one parameter set of the config.  With a table registered, env e runs FlyDyn on its own constants
  *     kp * m0, kd * m1, effort * m2, mass * m3 and inertia[i] * m3, mu * m4, gravity * m5   (fp32, rounded once each)

@@ -1,0 +1,407 @@
+"""GPU (-m gpu): the episode-aware advantage estimate (csrc/gae_episodic.hip) through the C ABI and through PPO.
+
+Every buffer a kernel writes sits between two sentinel guards and is pre-filled with the sentinel (as in
+tests/test_rollout_kernels_gpu.py).  References and bounds: tests/gae_episodic_ref.py.
+  lane = env    bit for bit the float32 restatement; against float64: target within 2 x its first-order bound (rollout_ref's
+                2^-23 (|gamma v'| + |tg|), plus the denormalisation's roundings under a table), advantage within 2 x the
+                first-order bound of the rounded intermediates
+  scan          targets as above (elementwise); advantage within 4 x (that bound + the restated carry bound) -- the margins
+                tests/test_rollout_kernels_gpu.py holds the existing scan to
+  exact stop    the scan's split of the time axis depends on T, so a rollout cut at an end is split differently and the rows
+                of OTHER chunks re-associate their carries differently; what "nothing passes an end" means bit for bit is
+                therefore checked twice: (a) at the same T, everything after the end replaced by values 1000 x larger leaves
+                every row at or before the end bit-identical; (b) the rows at or before the end in the end's own chunk equal
+                the float32 restatement of the rollout truncated at that end, bit for bit
+  moments       count exact, mean rtol 1e-10 / atol 1e-12, variance rtol 1e-10: tests/test_value_norm_gpu.py's bar."""
+import contextlib
+import ctypes as C
+import functools
+import io
+
+import numpy as np
+import pytest
+import torch
+
+from tests import gae_episodic_ref as E
+from tests import rollout_ref as R
+from tests import value_norm_ref as V
+from tests.hip_helpers import make_args
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+GUARD = 64
+SENTINEL = 12345.0
+MAXLEN = 50
+G32, GL32 = R.gamma_gl32()
+TABLE_S = (1000.0, 37.5, 44444.0)            # mean 37.5, std ~ 211: tests/test_value_norm_gpu.py's non-trivial table
+IDENTITY = np.array([0.0, 1.0, 1.0, 0.0], np.float32)
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from fly_bproject_amd import _lib
+    _lib.load()
+    return _lib
+
+
+class Guarded:
+    """A device array of n elements between two sentinel guards, pre-filled with the sentinel."""
+
+    def __init__(self, n, dtype=torch.float32):
+        self.n = int(n)
+        self.full = torch.full((2 * GUARD + self.n,), SENTINEL, dtype=dtype, device=DEV)
+        self.ptr = C.c_void_p(self.full.data_ptr() + GUARD * self.full.element_size())
+
+    def get(self):
+        torch.cuda.synchronize()
+        full = self.full.cpu().numpy()
+        assert (full[:GUARD] == SENTINEL).all(), "a kernel wrote in front of its array"
+        assert (full[GUARD + self.n:] == SENTINEL).all(), "a kernel wrote past the end of its array"
+        return full[GUARD:GUARD + self.n].copy()
+
+
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def _p(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def run_episodic(lib, case, mode, table=None, expect=0, T=None, N=None, null=None, maxlen=MAXLEN):
+    """-> (target, adv[, sets]); with expect != 0 asserts the return code and that nothing was written."""
+    r, v, vn, reset, progress, prev = case
+    T0, N0 = r.shape
+    T, N = T0 if T is None else T, N0 if N is None else N
+    tgt, adv = Guarded(T0 * N0), Guarded(T0 * N0)
+    d = {k: _dev(x) for k, x in zip(("r", "v", "vn", "reset", "progress", "prev"), case)}
+    if null is not None:
+        d[null] = None
+    L = lib.load()
+    if table is None:
+        rc = L.ppo_td_gae_episodic(_p(d["r"]), _p(d["v"]), _p(d["vn"]), _p(d["reset"]), _p(d["progress"]), _p(d["prev"]), maxlen,
+                                   0.99, 0.95, T, N, tgt.ptr, adv.ptr, mode, None)
+        sets = None
+    else:
+        sets = Guarded(lib.VALUE_NORM_SETS * lib.VALUE_NORM_SET, dtype=torch.float64)
+        dt = _dev(table)
+        rc = L.ppo_td_gae_episodic_vnorm(_p(d["r"]), _p(d["v"]), _p(d["vn"]), _p(d["reset"]), _p(d["progress"]), _p(d["prev"]),
+                                         maxlen, _p(dt), 0.99, 0.95, T, N, tgt.ptr, adv.ptr, sets.ptr, mode, None)
+    assert rc == expect, (rc, L.fly_last_error())
+    out = [tgt.get().reshape(T0, N0), adv.get().reshape(T0, N0)]
+    if expect != 0:
+        assert (out[0] == SENTINEL).all() and (out[1] == SENTINEL).all()
+        if sets is not None:
+            assert (sets.get() == SENTINEL).all()
+    if sets is not None:
+        out.append(sets.get().reshape(-1, 3))
+    return out
+
+
+def run_plain_gae(lib, r, v, vn, d, mode):
+    T, N = r.shape
+    tgt, adv = Guarded(T * N), Guarded(T * N)
+    dr, dv, dvn, dd = _dev(r), _dev(v), _dev(vn), _dev(d)
+    lib.check(lib.load().ppo_td_gae(_p(dr), _p(dv), _p(dvn), _p(dd), 0.99, 0.95, T, N, tgt.ptr, adv.ptr, mode, None), "ppo_td_gae")
+    return tgt.get().reshape(T, N), adv.get().reshape(T, N)
+
+
+# ----------------------------------------------------------------------------------------------------------------- cases
+def _values(T, N, seed):
+    rng = np.random.default_rng(seed)
+    return (rng.normal(0.5, 1, (T, N)).astype(np.float32), rng.normal(0, 1, (T, N)).astype(np.float32),
+            rng.normal(0, 1, (T, N)).astype(np.float32))
+
+
+@functools.lru_cache(maxsize=None)
+def lane_case(T, N):
+    """Deterministic flags.  Env e by e mod 3: 0 = no end (but progress at the limit somewhere: no flag, no end); 1 = carried-in
+    end, falls at t = 1 and t = 2 (consecutive); 2 = a fall at t = 0 and a time-out at t = T - 1; envs >= 3 of kinds 1 and 2
+    get more ends at random steps, falls and time-outs (at and beyond the limit) mixed.  T = 1: a single time-out."""
+    rng = np.random.default_rng(100 * T + N)
+    r, v, vn = _values(T, N, 7 * T + N)
+    reset = np.zeros((T, N), np.int64)
+    progress = rng.integers(1, MAXLEN - 1, (T, N)).astype(np.int64)
+    prev = np.zeros(N, np.int64)
+    if T < 5:
+        reset[0, 0], progress[0, 0] = 1, MAXLEN - 1
+    else:
+        for e in range(N):
+            k = e % 3
+            if k == 0:
+                progress[T // 2, e] = MAXLEN - 1
+                continue
+            if e >= 3:
+                more = rng.random(T) < 0.08
+                reset[more, e] = 1
+                late = more & (rng.random(T) < 0.5)
+                progress[late, e] = MAXLEN - 1 + rng.integers(0, 3, int(late.sum()))
+            if k == 1:
+                prev[e] = 1
+                reset[1:3, e] = 1
+                progress[1:3, e] = 5
+            else:
+                reset[0, e], progress[0, e] = 1, 3
+                reset[T - 1, e], progress[T - 1, e] = 1, MAXLEN - 1
+    return r, v, vn, reset, progress, prev
+
+
+def assert_every_kind(case):
+    r, v, vn, reset, progress, prev = case
+    T = r.shape[0]
+    ended, timeout, stale = E.flags_of(reset, progress, prev, MAXLEN)
+    assert (ended & ~timeout & ~stale).any(), "no fall"
+    assert (timeout & ~stale).any(), "no time-out"
+    assert (ended[1:] & ended[:-1]).any(), "no two consecutive ends"
+    assert ended[0].any() and ended[T - 1].any(), "no end at t = 0 or at T - 1"
+    assert (prev != 0).any(), "no env with ended_prev"
+    assert (~ended.any(axis=0) & (prev == 0)).any(), "no env without an end"
+    assert ((progress >= MAXLEN - 1) & ~ended).any(), "no progress at the limit without the flag"
+
+
+def check_lane(case, tgt, adv, table=None):
+    t32, a32 = E.episodic32(*case, MAXLEN, table)
+    assert np.array_equal(tgt, t32) and np.array_equal(adv, a32)
+    ref = E.episodic64(*case, MAXLEN, G32, GL32, table)
+    assert (np.abs(tgt - ref.target) <= 2 * ref.target_err).all()
+    assert (np.abs(adv - ref.adv) <= 2 * ref.bound).all()
+    return ref
+
+
+LANE_SHAPES = [(1, 1), (5, 3), (80, 257), (64, 300)]
+
+
+@pytest.mark.parametrize("T,N", LANE_SHAPES)
+def test_lane_form(lib, T, N):
+    case = lane_case(T, N)
+    if T >= 5:
+        assert_every_kind(case)
+    tgt, adv = run_episodic(lib, case, 0)
+    check_lane(case, tgt, adv)
+    stale = E.flags_of(*case[3:], MAXLEN)[2]
+    assert (adv[stale] == 0).all() and np.array_equal(tgt[stale], case[1][stale])
+
+
+# ------------------------------------------------------------------------------------------------------------------ scan
+SCAN_SHAPES = [(65, 1), (1025, 3), (4097, 2)]
+SCAN_MARGIN = 4
+
+
+@functools.lru_cache(maxsize=None)
+def scan_case(T, N):
+    """Ends at the chunk boundaries of the scan's split: env e ends at the last step of chunk 2 + e, at the first step of the
+    chunk that follows chunk 5 + e in time, at t = 0 (T = 65: the one step of the ragged last lane) and at T - 1; falls and
+    time-outs alternate; env 1 carries an end in."""
+    rng = np.random.default_rng(100 * T + N)
+    r, v, vn = _values(T, N, 7 * T + N)
+    reset = np.zeros((T, N), np.int64)
+    progress = rng.integers(1, MAXLEN - 1, (T, N)).astype(np.int64)
+    prev = np.zeros(N, np.int64)
+    chunks = R.scan_chunks(T)
+    ends = []
+    for e in range(N):
+        last_of = chunks[2 + e][1] - 1                       # the last step of a chunk
+        first_of = chunks[5 + e][1]                          # the first step of the next chunk in time
+        assert first_of == chunks[4 + e][0]
+        for k, t in enumerate((last_of, first_of, 0, T - 1)):
+            reset[t, e] = 1
+            if (k + e) % 2:
+                progress[t, e] = MAXLEN - 1
+            ends.append((t, e))
+    if N > 1:
+        prev[1] = 1
+    if T == 65:
+        assert chunks[-1] == (0, 1)                          # a lane whose only step holds an end
+    return (r, v, vn, reset, progress, prev), tuple(ends)
+
+
+def check_scan(case, tgt, adv, table=None):
+    ref = E.episodic64(*case, MAXLEN, G32, GL32, table)
+    t32, _ = E.episodic32(*case, MAXLEN, table)
+    assert np.array_equal(tgt, t32)                          # the targets are elementwise
+    assert (np.abs(tgt - ref.target) <= 2 * ref.target_err).all()
+    bound = ref.bound + E.scan_carry_bound64_masked(ref.delta, ref.live, GL32)
+    err = np.abs(adv - ref.adv)
+    ok = bound > 0
+    print("episodic scan T=%d N=%d: max advantage error / bound %.3f" % (adv.shape + (float((err[ok] / bound[ok]).max()),)))
+    assert (err <= SCAN_MARGIN * bound).all()
+
+
+@pytest.mark.parametrize("T,N", SCAN_SHAPES)
+def test_scan_form(lib, T, N):
+    case, ends = scan_case(T, N)
+    tgt, adv = run_episodic(lib, case, R.GAE_SCAN)
+    check_scan(case, tgt, adv)
+    r, v, vn, reset, progress, prev = case
+    L = -(-T // 64)
+    for t_e, e in ends:
+        # (a) the same split, everything after the end 1000 x larger: no row at or before the end moves by a bit
+        loud = [x.copy() for x in (r, v, vn)]
+        for x in loud:
+            x[t_e + 1:] = x[t_e + 1:] * np.float32(-1000.0) + np.float32(3.0)
+        t2, a2 = run_episodic(lib, (*loud, reset, progress, prev), R.GAE_SCAN)
+        assert np.array_equal(t2[:t_e + 1, e], tgt[:t_e + 1, e]) and np.array_equal(a2[:t_e + 1, e], adv[:t_e + 1, e]), (t_e, e)
+        if t_e + 1 < T:
+            assert not np.array_equal(a2[t_e + 1:, e], adv[t_e + 1:, e])
+        # (b) the rollout truncated at the end, sequentially in float32: the end's own chunk, bit for bit
+        lo = T - ((T - 1 - t_e) // L + 1) * L
+        lo = max(lo, 0)
+        cut = tuple(x[:t_e + 1] for x in (r, v, vn, reset, progress)) + (prev,)
+        t3, a3 = E.episodic32(*cut, MAXLEN)
+        assert np.array_equal(t3[lo:, e], tgt[lo:t_e + 1, e]) and np.array_equal(a3[lo:, e], adv[lo:t_e + 1, e]), (t_e, e, lo)
+
+
+# -------------------------------------------------------------------------------------------------- identity, value norm
+@pytest.mark.parametrize("T,N,scan", [(80, 257, False), (5, 3, False), (1025, 3, True), (65, 1, True)])
+def test_no_flags_is_td_gae_mode_3(lib, T, N, scan):
+    """Every flag zero: ppo_td_gae with per-step done = 1 and the masked recurrence, bit for bit.  The existing scan form
+    refuses the masked recurrence, so the scan is held to ppo_td_gae's scan in mode PPO_GAE_DONE_PER_STEP with done = 1 --
+    with done = 1 the mask multiplies by one, and the chunking, the multipliers and the pair scan are the same operations."""
+    r, v, vn = _values(T, N, T + N)
+    z = np.zeros((T, N), np.int64)
+    case = (r, v, vn, z, z + MAXLEN, np.zeros(N, np.int64))              # progress at the limit everywhere: no flag, no end
+    ones = np.ones((T, N), np.float32)
+    tgt, adv = run_episodic(lib, case, R.GAE_SCAN if scan else 0)
+    t0, a0 = run_plain_gae(lib, r, v, vn, ones, (R.GAE_SCAN | R.GAE_DONE_PER_STEP) if scan else 3)
+    assert np.array_equal(tgt, t0) and np.array_equal(adv, a0)
+
+
+@pytest.mark.parametrize("T,N,scan", [(80, 257, False), (64, 300, False), (1025, 3, True), (65, 1, True)])
+def test_vnorm_identity_table_is_the_plain_kernel(lib, T, N, scan):
+    case = scan_case(T, N)[0] if scan else lane_case(T, N)
+    mode = R.GAE_SCAN if scan else 0
+    tgt, adv = run_episodic(lib, case, mode)
+    t1, a1, sets = run_episodic(lib, case, mode, table=IDENTITY)
+    assert np.array_equal(tgt, t1) and np.array_equal(adv, a1)
+    assert sets[:, 0].sum() == T * N
+
+
+def _merged(lib, sets):
+    stats = torch.tensor(V.initial(), dtype=torch.float64, device=DEV)
+    dsets = _dev(sets)
+    out, table = Guarded(3, dtype=torch.float64), Guarded(4)
+    lib.check(lib.load().ppo_value_norm_merge(_p(stats), _p(dsets), dsets.shape[0], out.ptr, table.ptr, None), "ppo_value_norm_merge")
+    return tuple(float(x) for x in out.get())
+
+
+def _assert_stats(got, want):
+    (c, mu, var), (wc, wmu, wvar) = got, want
+    print("target statistics: count %r (want %r)  mean %.17g (want %.17g)  var %.17g (want %.17g)" % (c, wc, mu, wmu, var, wvar))
+    assert c == wc
+    np.testing.assert_allclose(mu, wmu, rtol=1e-10, atol=1e-12)
+    np.testing.assert_allclose(var, wvar, rtol=1e-10, atol=0)
+
+
+@pytest.mark.parametrize("T,N,scan", [(80, 257, False), (64, 300, False), (5, 3, False), (1025, 3, True), (4097, 2, True)])
+def test_vnorm_nontrivial_table(lib, T, N, scan):
+    """Critic outputs of unit scale under mean 37.5 / std ~ 211, rewards x 20: the reference (bit for bit in the lane form, the
+    scan within its bound), and the merged moments of the targets against float64."""
+    case = scan_case(T, N)[0] if scan else lane_case(T, N)
+    case = ((case[0] * 20).astype(np.float32),) + tuple(case[1:])
+    table = V.table(TABLE_S)
+    tgt, adv, sets = run_episodic(lib, case, R.GAE_SCAN if scan else 0, table=table)
+    if scan:
+        check_scan(case, tgt, adv, table)
+    else:
+        check_lane(case, tgt, adv, table)
+    stale = E.flags_of(*case[3:], MAXLEN)[2]
+    assert np.array_equal(tgt[stale], V.denormalize(case[1], table)[stale]) and (adv[stale] == 0).all()
+    assert sets[:, 0].sum() == T * N
+    _assert_stats(_merged(lib, sets), V.moments(tgt))
+    ref = E.episodic64(*case, MAXLEN, G32, GL32, table)
+    assert ref.moments[0] == T * N
+    np.testing.assert_allclose(_merged(lib, sets)[1], ref.moments[1], rtol=0, atol=2 * np.abs(ref.target_err).max())
+
+
+# ------------------------------------------------------------------------------------------------------- argument checks
+def test_argument_checks(lib):
+    case = lane_case(5, 3)
+    for table in (None, IDENTITY):
+        for null in ("r", "v", "vn", "reset", "progress", "prev"):
+            run_episodic(lib, case, 0, table=table, expect=-1, null=null)
+        run_episodic(lib, case, 0, table=table, expect=-1, T=0)
+        run_episodic(lib, case, 0, table=table, expect=-1, N=0)
+        run_episodic(lib, case, 0, table=table, expect=-1, maxlen=0)
+        for mode in (1, 2, 3, 8, R.GAE_SCAN | 2, R.GAE_SCAN | 1, -1):
+            run_episodic(lib, case, mode, table=table, expect=-1)
+    L = lib.load()
+    d = [_dev(x) for x in case]
+    out = Guarded(15)
+    args = [_p(x) for x in d] + [MAXLEN, 0.99, 0.95, 5, 3]
+    assert L.ppo_td_gae_episodic(*args, None, out.ptr, 0, None) == -1
+    assert L.ppo_td_gae_episodic(*args, out.ptr, None, 0, None) == -1
+    tab = _dev(IDENTITY)
+    args = [_p(x) for x in d] + [MAXLEN, _p(tab), 0.99, 0.95, 5, 3]
+    assert L.ppo_td_gae_episodic_vnorm(*args, out.ptr, out.ptr, None, 0, None) == -1
+    assert L.ppo_td_gae_episodic_vnorm(*args[:7], None, *args[8:], out.ptr, out.ptr, out.ptr, 0, None) == -1
+    assert (out.get() == SENTINEL).all()
+
+
+# ------------------------------------------------------------------------------------------------------------ end to end
+def _rollout(persistent, seen):
+    from fly_bproject_amd.fly import Fly
+    from fly_bproject_amd.params import default_params
+    from fly_bproject_amd.ppo import PPO
+    n = 4096
+    torch.manual_seed(0)
+    args = make_args(n, persistent_rollout=persistent, gae="episodic")
+    params = default_params(n, "bigGrav", "standing")
+    params.max_episode_length = 37
+    with contextlib.redirect_stdout(io.StringIO()):
+        agent = PPO(args, env=Fly(args, params=params))
+        assert agent.persistent_rollout == persistent and agent.rollout_size == 160 and agent.env.max_episode_length == 37
+        real_update = agent.update
+
+        def checked_update():
+            agent.make_data()
+            for name in ("_reset_rows", "_progress_rows", "_ended_prev", "_target", "all_advantage", "_v_ring", "all_reward"):
+                seen[name] = getattr(agent, name).cpu().numpy().copy()
+            real_update()
+
+        agent.update = checked_update
+        for _ in range(agent.rollout_size):
+            agent.run()
+        agent.flush_log()
+        agent._check_step_counter()
+    torch.cuda.synchronize()
+    assert agent.optim_step == 75 and int(agent.policy.step.item()) == agent.policy.steps_issued
+    with pytest.raises(ValueError, match="all_done"):
+        agent.all_done = torch.ones(1)
+    agent.exit()
+
+
+def test_ppo_end_to_end_both_rollout_forms():
+    """4096 envs, T = 160, max_episode_length = 37: one rollout, make_data and one update in the one-launch form and in the
+    per-step form from the same seed."""
+    a, b = {}, {}
+    _rollout(True, a)
+    _rollout(False, b)
+    for name in a:
+        assert np.array_equal(a[name], b[name]), name
+    T = 160
+    ended, timeout, stale = E.flags_of(a["_reset_rows"], a["_progress_rows"], a["_ended_prev"], 37)
+    # An episode that runs into the limit lasts 36 steps (the step that resets leaves progress 1, the flag rises at 36), one
+    # that falls at most 35, and the unfinished one at the rollout's end fewer than 36.  For an env with k time-outs and f
+    # falls therefore 160 < 36 k + 35 f + 36: an env that never falls runs into the limit exactly four times (36 * 4 <= 160),
+    # and every fall costs at most one of the four.
+    n_out, n_fall = timeout.sum(axis=0), (ended & ~timeout).sum(axis=0)
+    print("time-outs per env: min %d max %d; envs that fell: %d of %d; min of 36 k + 35 f: %d"
+          % (n_out.min(), n_out.max(), (n_fall > 0).sum(), n_fall.size, (36 * n_out + 35 * n_fall).min()))
+    assert (n_out[n_fall == 0] == 4).all() and (n_fall == 0).any()
+    assert (36 * n_out + 35 * n_fall > 124).all()
+    assert stale[0].all() and (a["_ended_prev"] == 1).all()  # the env starts with reset_buf = 1: row 0 performs the first reset
+    v = a["_v_ring"][..., 0]
+    t32, a32 = E.episodic32(a["all_reward"][..., 0], v[:T], v[1:], a["_reset_rows"], a["_progress_rows"], a["_ended_prev"], 37)
+    assert np.array_equal(a["_target"][..., 0], t32) and np.array_equal(a["all_advantage"][..., 0], a32)
+    assert (a["all_advantage"][0] == 0).all() and np.array_equal(a["_target"][0, :, 0], v[0])
+
+
+def test_bad_gae_value_and_reference_default():
+    from fly_bproject_amd.ppo import PPO
+    with contextlib.redirect_stdout(io.StringIO()):
+        with pytest.raises(ValueError, match="gae"):
+            PPO(make_args(4096, gae="lambda"))
+        agent = PPO(make_args(4096))
+    assert agent.gae == "reference" and agent._ended_prev is None and agent._reset_rows is None
+    agent.all_done = None                                    # the reference path keeps its setter
+    agent.exit()

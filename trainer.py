@@ -12,6 +12,8 @@ loaded with it; such a checkpoint needs `--normalize_obs` to load.
 `--normalize_value` (running mean / std normalisation of the critic's regression targets; off by default): the critic's
 outputs are mapped back to reward units wherever they meet rewards; the statistics are saved with the checkpoint as
 value_rms.* and loaded with it; such a checkpoint needs `--normalize_value` to load.
+`--gae episodic` (episode-aware advantage estimate with time-limit bootstrapping; the default `reference` is
+the reference's estimator with its quirks).
 `--randomize` (per-env physics domain randomisation, off by default): each env runs on its own multipliers of kp, kd, effort,
 mass (and inertia), mu and gravity, drawn from `--dr_<name> LO HI` at every reset of that env with seed `--dr_seed` (default
 `--seed`; rank r adds r * 0x9E3779B9).  A property of the env: nothing of it goes into the checkpoint.
@@ -71,6 +73,12 @@ def parse_args(argv=None):
                         help='the critic regresses on TD targets normalised by their running mean / std, and its outputs are '
                              'mapped back to reward units for the TD target and GAE (rl_games normalize_value, without its clamp; '
                              'not in the reference; off by default)')
+    parser.add_argument('--gae', type=str, default="reference", choices=["reference", "episodic"],
+                        help='advantage estimator: reference = ppo.py:157-171 as it stands (the done mask of the last step over the '
+                             'whole rollout, no reset of the recurrence at episode ends); episodic = per-step end flags, the '
+                             'recurrence stops at every episode end, time-outs bootstrap from the value of the next observation '
+                             '(rl_games value_bootstrap / time_outs) and the step that performs a reset trains nothing.  episodic '
+                             'is NOT the reference\'s estimator; off by default')
     parser.add_argument('--obs_clip', type=float, default=5.0, help='bound of a normalised observation (with --normalize_obs)')
     parser.add_argument('--randomize', action='store_true',
                         help='per-env physics domain randomisation, redrawn at every reset of the env (Isaac Gym actor-property '
