@@ -381,6 +381,17 @@ __device__ __forceinline__ void df_q_row(const DfLds& L, const float* bias3, int
     q[3] = (((p0.w + p1.w) + p2.w) + p3.w) + b.w;
 }
 
+// the lane's four columns of dZ3: `dq` in the taken action's column, 0 elsewhere
+__device__ __forceinline__ float4 fs_dqn_dz3(int lq, int idx, float dq)
+{
+    float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (4 * lq + 0 == idx) d.x = dq;
+    if (4 * lq + 1 == idx) d.y = dq;
+    if (4 * lq + 2 == idx) d.z = dq;
+    if (4 * lq + 3 == idx) d.w = dq;
+    return d;
+}
+
 struct DqnChunk { const float *obs, *next_obs, *act, *reward, *done; };      // one sampled replay step: n rows each (device pointers)
 
 constexpr long DF_STRIDE1 = (long)DQN_H * DQN_IN_PAD + DQN_H, DF_STRIDE2 = (long)DQN_H * DQN_H + DQN_H,
@@ -506,32 +517,18 @@ __global__ __launch_bounds__(THREADS, 1) void dqn_chain_kernel(
         {   // ---- TD target, Huber, d loss / d Q (dqn.py:69-79): eight lanes per row, four Q columns each -------------------------
             float q[4];
             df_q_row(L, L.bias + 2 * DQN_H, tl, q);
-            const float a01 = 0.5f * (r_act + 1.0f);
-            int idx = (int)rintf(a01 * (float)(DQN_NACT - 1));                 // torch.round: half to even (dqn.py:70)
-            idx = idx < 0 ? 0 : (idx >= DQN_NACT ? DQN_NACT - 1 : idx);
+            const int idx = dqn_action_index(r_act, DQN_NACT);                 // (dqn.py:70)
             float sel = 0.0f;
 #pragma unroll
             for (int j = 0; j < 4; ++j) sel = (4 * lq + j == idx) ? q[j] : sel;
             const float q_val = fs_sum8(sel);                                  // one non-zero among the eight lanes: exact
-            const float target = r_rew + discount * qn_max * r_done;
-            const float dv = q_val - target;
-            const float hub = fabsf(dv) < 1.0f ? 0.5f * dv * dv : fabsf(dv) - 0.5f;      // smooth_l1, beta = 1
-            const float dq = inv_B * fminf(fmaxf(dv, -1.0f), 1.0f);
-            float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (4 * lq + 0 == idx) d.x = dq;
-            if (4 * lq + 1 == idx) d.y = dq;
-            if (4 * lq + 2 == idx) d.z = dq;
-            if (4 * lq + 3 == idx) d.w = dq;
-            fs_store4<FS_P4>(L.Z3, lrow, 4 * lq, d);
-            if (lq == 0) L.rowloss[lrow] = hub;
+            const DqnTdRow t = dqn_td_row(q_val, r_rew, discount, qn_max, r_done, inv_B);
+            fs_store4<FS_P4>(L.Z3, lrow, 4 * lq, fs_dqn_dz3(lq, idx, t.dq));
+            if (lq == 0) L.rowloss[lrow] = t.hub;
         }
         __syncthreads();
         df_stamp(sb, 10);
-        if (tl < 32) {      // fixed-order sum of the tile's Huber terms
-            float hub = L.rowloss[tl];
-            for (int o = 16; o > 0; o >>= 1) hub += __shfl_down(hub, o, 32);
-            if (tl == 0) loss_part[tile] = hub;
-        }
+        if (tl < 32) tile_loss_sum<1>(L.rowloss, tl, loss_part + tile);
         FsTr tr1, trx, tr4;
         fs_tr_init<FS_P1>(tr1, lane);
         fs_tr_init<FS_PX>(trx, lane);

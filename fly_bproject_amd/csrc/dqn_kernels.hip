@@ -11,6 +11,8 @@
 
 namespace {
 
+#include "loss_head.inc"
+
 __global__ __launch_bounds__(256) void dqn_eps_greedy_kernel(const float* __restrict__ q, const float* __restrict__ coin_u,
                                                              const float* __restrict__ rand_u, float epsilon, int A,
                                                              float* __restrict__ act_out, long n)
@@ -38,18 +40,15 @@ __global__ __launch_bounds__(256) void dqn_huber_td_kernel(const float* __restri
     const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
     float hub = 0.0f;
     if (b < B) {
-        const float a01 = 0.5f * (act[b] + 1.0f);
-        int idx = (int)rintf(a01 * (float)(A - 1));             // torch.round: half to even
-        idx = idx < 0 ? 0 : (idx >= A ? A - 1 : idx);
+        const int idx = dqn_action_index(act[b], A);
         const float* qn = q_next + b * A;
         float mx = qn[0];
         for (int a = 1; a < A; ++a) mx = fmaxf(mx, qn[a]);
-        const float target = reward[b] + discount * mx * done[b];
-        const float d = q_table[b * A + idx] - target;
-        hub = fabsf(d) < 1.0f ? 0.5f * d * d : fabsf(d) - 0.5f;  // smooth_l1, beta = 1
+        const DqnTdRow t = dqn_td_row(q_table[b * A + idx], reward[b], discount, mx, done[b], inv_B);
+        hub = t.hub;
         float* g = dq + b * A;
         for (int a = 0; a < A; ++a) g[a] = 0.0f;
-        g[idx] = inv_B * fminf(fmaxf(d, -1.0f), 1.0f);
+        g[idx] = t.dq;
     }
     for (int o = 32; o > 0; o >>= 1) hub += __shfl_down(hub, o, 64);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = hub;

@@ -22,6 +22,7 @@
 
 namespace {
 
+#include "loss_head.inc"
 #include "mlp_gemm.inc"
 #include "grad_w_layer.inc"
 #include "fs_common.inc"
@@ -269,17 +270,12 @@ __global__ __launch_bounds__(THREADS, 2) void dqn_td_kernel(
         const bool in = row < nvalid;
         float d = 0.0f, hub = 0.0f;
         int idx = 0;
-        if (in) {
-            const float a01 = 0.5f * (act[row0 + row] + 1.0f);
-            idx = (int)rintf(a01 * (float)(DQN_NACT - 1));                                // torch.round: half to even (dqn.py:70)
-            idx = idx < 0 ? 0 : (idx >= DQN_NACT ? DQN_NACT - 1 : idx);
-        }
+        if (in) idx = dqn_action_index(act[row0 + row], DQN_NACT);                        // (dqn.py:70)
         const float q_val = __shfl(qv[k], idx, 32);                                       // q_table[b, act] (dqn.py:71)
         if (in) {
-            const float target = reward[row0 + row] + discount * qn_max[k] * done[row0 + row];
-            const float dv = q_val - target;
-            hub = fabsf(dv) < 1.0f ? 0.5f * dv * dv : fabsf(dv) - 0.5f;                    // smooth_l1, beta = 1
-            if (col == idx) d = inv_B * fminf(fmaxf(dv, -1.0f), 1.0f);
+            const DqnTdRow t = dqn_td_row(q_val, reward[row0 + row], discount, qn_max[k], done[row0 + row], inv_B);
+            hub = t.hub;
+            if (col == idx) d = t.dq;
             dz3_t[frag_off(row, col)] = d;
         }
         ldsZ3[row * (DQN_OUT + 4) + col] = d;
@@ -287,11 +283,7 @@ __global__ __launch_bounds__(THREADS, 2) void dqn_td_kernel(
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's h1 / h2 stores are acknowledged before anyone re-reads them
     __syncthreads();
-    if (tid < 32) {
-        float hub = rowloss[tid];
-        for (int o = 16; o > 0; o >>= 1) hub += __shfl_down(hub, o, 32);
-        if (tid == 0) loss_part[tile] = hub;
-    }
+    if (tid < 32) tile_loss_sum<1>(rowloss, tid, loss_part + tile);
     {   // dA2 = dZ3 . W3 -> dZ2 (arena A; the split-K partials there are consumed)
         f32x16 acc[2];
         tile_gemm<DQN_OUT, 2>(PT + DQN_OFF_T3, 2 * wave, ldsZ3, acc, lane);

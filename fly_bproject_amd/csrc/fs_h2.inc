@@ -19,7 +19,7 @@ constexpr int H2C_X = 0, H2C_H1 = 1, H2C_H2 = 2, H2C_H3 = 3, H2C_Z4 = 4, H2C_Z3 
               H2C_W4 = 11, H2_NACT_CLASSES = 8, H2_FSC_INV = 16, H2_FSC_FLOATS = 48;
 // Where a class maximum is steered (scaled): activations (x, h1 .. h3) into [2^7, 2^8) -- 256x below fp16's largest number; their maxima
 // move by <= 4 binades from one minibatch to the next (tools/h2_scale_trace.py, real updates) --; gradients (dz4 .. dz1) into [2^2, 2^3):
-// the PPO surrogate is unclipped on one side (A < 0, ratio large: ppo.py:191-193), so a few rows carry gradients 10^3 .. 10^5 x the
+// the PPO surrogate (ppo_row_loss, loss_head.inc) is unclipped on one side (A < 0, ratio large: ppo.py:191-193), so a few rows carry gradients 10^3 .. 10^5 x the
 // rest and a class maximum RISES by up to 10.5 binades from one launch to the next (tools/h2_scale_trace.py 30 8192); 13 binades of
 // headroom cover that.  What the low target costs: an element has an absolute error of max(2^-25, 2^-24 |scaled|), i.e. full
 // precision down to 2^-2 .. 2^-3 of its class maximum and 2^-27 OF THE MAXIMUM below.  That is NOT enough where a few rows carry the

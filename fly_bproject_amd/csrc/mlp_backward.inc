@@ -5,8 +5,8 @@
 // One 32-row tile per workgroup.  The loss (ppo.py:191-194) is
 //     mean_i( -min(ratio_i A_i, clamp(ratio_i, 1-c, 1+c) A_i) ) + mean_i huber(v_i - target_i)
 // with ratio_i = exp(logp_i - old_logp_i) and logp the diagonal-Gaussian log-density of the
-// stored action under the CURRENT variance.  Gradients follow torch's subgradient choices:
-// min() splits a tie evenly, clamp() passes gradient on the closed interval.
+// stored action under the CURRENT variance.  The row's loss terms and their gradient, torch's
+// subgradient choices included, are ppo_row_loss in loss_head.inc, shared with the fused kernels.
 //   dz4 [n][32]: cols 0..17 d/d(pre-ELU mean), col 18 d/d(value), rest 0
 //   dz3 [n][128], dz2 [n][128], dz1 [n][256]: gradients at the pre-activations of layers 3,2,1
 //   loss_part [grid][2]: per-workgroup sums of the policy term and of the Huber term
@@ -66,6 +66,60 @@ constexpr int BW_Z4 = BW_Z3 + BM * (MLP_H3 + 4);           // [32][36]
 constexpr int BW_TAIL = BW_Z4 + BM * (MLP_OUT + 4);        // [32][2] per-row loss terms
 constexpr int BW_FLOATS = BW_TAIL + 2 * BM;                // 38.9 KB
 
+// Loss gradient at the outputs of one tile, one thread per (row, output column), for both arithmetics: the 32 lanes of a
+// row reduce the Mahalanobis term and log-determinant with a fixed xor butterfly, every lane then holds the row's loss
+// terms (ppo_row_loss, loss_head.inc) and writes its own column of dZ4 -- to HBM and, through `store_z4(row, col, d)`,
+// to the LDS operand of the next GEMM in that arithmetic's form.  Ends with the workgroup's barrier and the tile's loss
+// partials.
+template <bool COH, class StoreZ4>
+__device__ __forceinline__ void ppo_loss_phase(
+    const long tile, const float* __restrict__ out_saved, const float* __restrict__ action,
+    const float* __restrict__ old_logp, const float* __restrict__ adv, const float* __restrict__ target,
+    const float* __restrict__ var, int nvalid, float inv_batch, float clip, float* __restrict__ dz4, float* rowloss,
+    float* __restrict__ loss_part, StoreZ4 store_z4)
+{
+    const int tid = threadIdx.x;
+    const long row0 = tile * BM;
+    const float* out_t = out_saved + row0 * MLP_OUT;       // wave-uniform tile bases, 32-bit lane offsets
+    const float* act_t = action + row0 * MLP_NACT;
+    const float* olp_t = old_logp + row0;
+    const float* adv_t = adv + row0;
+    const float* tgt_t = target + row0;
+    float* dz4_t = dz4 + row0 * MLP_OUT;
+    const int col = tid & 31;
+    const bool act = col < MLP_NACT;
+    const float L = act ? sqrtf(var[col]) : 1.0f;
+    const float inv_L = 1.0f / L, inv_var = act ? 1.0f / var[col] : 0.0f;       // one division each per thread, not per element
+    float half_log_det = act ? logf(L) : 0.0f;
+#pragma unroll
+    for (int o = 1; o < 32; o <<= 1) half_log_det += __shfl_xor(half_log_det, o, 32);
+#pragma unroll
+    for (int k = 0; k < BM * MLP_OUT / THREADS; ++k) {
+        const int row = (tid >> 5) + k * (THREADS / 32);
+        const bool in = row < nvalid;
+        const float y = in ? gload1<COH>(out_t, frag_off(row, col)) : 0.0f;                   // mean (cols 0..17), value (col 18)
+        const float a = (in && act) ? act_t[row * MLP_NACT + col] : 0.0f;
+        const float xj = act ? (a - y) * inv_L : 0.0f;
+        float M = xj * xj;
+#pragma unroll
+        for (int o = 1; o < 32; o <<= 1) M += __shfl_xor(M, o, 32);
+        float d = 0.0f, pol = 0.0f, hub = 0.0f;
+        if (in) {
+            const PpoRowLoss r = ppo_row_loss<false>(M, half_log_det, olp_t[row], adv_t[row], __shfl(y, MLP_NACT, 32), tgt_t[row],
+                                                     inv_batch, clip);
+            pol = r.pol;
+            hub = r.hub;
+            if (act) d = ppo_mean_dz4(r.c, a, y, inv_var);
+            else if (col == MLP_NACT) d = r.dv;
+            dz4_t[frag_off(row, col)] = d;
+        }
+        store_z4(row, col, d);
+        if (col == 0) { rowloss[2 * row] = pol; rowloss[2 * row + 1] = hub; }
+    }
+    __syncthreads();
+    if (tid < 32 && loss_part) tile_loss_sum<2>(rowloss, tid, loss_part + 2 * tile);
+}
+
 template <bool COH = false>
 __device__ __forceinline__ void backward_body(
     float* lds, const long tile,
@@ -89,64 +143,9 @@ __device__ __forceinline__ void backward_body(
     HFrag<1> hf3;
     hfrag_load<MLP_H3, 1, COH>(hf3, h3_saved + row0 * MLP_H3, nvalid, wave * 32, lane);     // in flight during the loss phase
 
-    // Loss gradient at the outputs, one thread per (row, output column): the 32 lanes of a row
-    // reduce the Mahalanobis term and log-determinant with a fixed xor butterfly, every lane then
-    // holds the row's d loss / d logp and writes its own column of dZ4 (HBM + the LDS operand).
-    {
-        const float* out_t = out_saved + row0 * MLP_OUT;       // wave-uniform tile bases, 32-bit lane offsets
-        const float* act_t = action + row0 * MLP_NACT;
-        const float* olp_t = old_logp + row0;
-        const float* adv_t = adv + row0;
-        const float* tgt_t = target + row0;
-        float* dz4_t = dz4 + row0 * MLP_OUT;
-        const int col = tid & 31;
-        const bool act = col < MLP_NACT;
-        const float L = act ? sqrtf(var[col]) : 1.0f;
-        const float inv_L = 1.0f / L, inv_var = act ? 1.0f / var[col] : 0.0f;       // one division each per thread, not per element
-        float half_log_det = act ? logf(L) : 0.0f;
-#pragma unroll
-        for (int o = 1; o < 32; o <<= 1) half_log_det += __shfl_xor(half_log_det, o, 32);
-#pragma unroll
-        for (int k = 0; k < BM * MLP_OUT / THREADS; ++k) {
-            const int row = (tid >> 5) + k * (THREADS / 32);
-            const bool in = row < nvalid;
-            const float y = in ? gload1<COH>(out_t, frag_off(row, col)) : 0.0f;                   // mean (cols 0..17), value (col 18)
-            const float a = (in && act) ? act_t[row * MLP_NACT + col] : 0.0f;
-            const float xj = act ? (a - y) * inv_L : 0.0f;
-            float M = xj * xj;
-#pragma unroll
-            for (int o = 1; o < 32; o <<= 1) M += __shfl_xor(M, o, 32);
-            float d = 0.0f, pol = 0.0f, hub = 0.0f;
-            if (in) {
-                const float logp = -0.5f * (33.08178959434617f + M) - half_log_det;
-                const float ratio = expf(logp - olp_t[row]);
-                const float A = adv_t[row];
-                const float s1 = ratio * A;
-                const float rc = fminf(fmaxf(ratio, 1.0f - clip), 1.0f + clip);
-                const float s2 = rc * A;
-                const float in_range = (ratio >= 1.0f - clip && ratio <= 1.0f + clip) ? 1.0f : 0.0f;
-                float dmin;                                    // d min(s1,s2) / d ratio
-                if (s1 < s2) dmin = A;
-                else if (s1 > s2) dmin = A * in_range;
-                else dmin = 0.5f * (A + A * in_range);
-                const float c = -inv_batch * ratio * dmin;     // d loss / d logp
-                pol = -fminf(s1, s2);
-                const float dv = __shfl(y, MLP_NACT, 32) - tgt_t[row];
-                hub = fabsf(dv) < 1.0f ? 0.5f * dv * dv : fabsf(dv) - 0.5f;
-                if (act) d = c * (a - y) * inv_var * elu_grad_from_out(y);
-                else if (col == MLP_NACT) d = inv_batch * fminf(fmaxf(dv, -1.0f), 1.0f);   // smooth_l1', beta = 1
-                dz4_t[frag_off(row, col)] = d;
-            }
-            ldsZ4[row * (MLP_OUT + 4) + col] = d;
-            if (col == 0) { rowloss[2 * row] = pol; rowloss[2 * row + 1] = hub; }
-        }
-    }
-    __syncthreads();
-    if (tid < 32 && loss_part) {       // fixed-order sum of the 32 rows' loss terms
-        float pol = rowloss[2 * tid], hub = rowloss[2 * tid + 1];
-        for (int o = 16; o > 0; o >>= 1) { pol += __shfl_down(pol, o, 32); hub += __shfl_down(hub, o, 32); }
-        if (tid == 0) { loss_part[2 * tile] = pol; loss_part[2 * tile + 1] = hub; }
-    }
+    // loss gradient at the outputs: dZ4 to HBM and to the LDS operand, the tile's loss partials (ends behind its barrier)
+    ppo_loss_phase<COH>(tile, out_saved, action, old_logp, adv, target, var, nvalid, inv_batch, clip, dz4, rowloss, loss_part,
+                        [&](int row, int col, float d) { ldsZ4[row * (MLP_OUT + 4) + col] = d; });
     HFrag<1> hf2;
     {   // dA3 = dZ4 . W4  ->  dZ3
         f32x16 acc[1];
@@ -221,69 +220,14 @@ __device__ __forceinline__ void backward_body_b3(
     HFrag<1> hf3;
     hfrag_load<MLP_H3, 1, COH>(hf3, h3_saved + row0 * MLP_H3, nvalid, wave * 32, lane);     // in flight during the loss phase
 
-    // Loss gradient at the outputs, one thread per (row, output column): the 32 lanes of a row
-    // reduce the Mahalanobis term and log-determinant with a fixed xor butterfly, every lane then
-    // holds the row's d loss / d logp and writes its own column of dZ4 (HBM + the LDS operand).
-    {
-        const float* out_t = out_saved + row0 * MLP_OUT;       // wave-uniform tile bases, 32-bit lane offsets
-        const float* act_t = action + row0 * MLP_NACT;
-        const float* olp_t = old_logp + row0;
-        const float* adv_t = adv + row0;
-        const float* tgt_t = target + row0;
-        float* dz4_t = dz4 + row0 * MLP_OUT;
-        const int col = tid & 31;
-        const bool act = col < MLP_NACT;
-        const float L = act ? sqrtf(var[col]) : 1.0f;
-        const float inv_L = 1.0f / L, inv_var = act ? 1.0f / var[col] : 0.0f;       // one division each per thread, not per element
-        float half_log_det = act ? logf(L) : 0.0f;
-#pragma unroll
-        for (int o = 1; o < 32; o <<= 1) half_log_det += __shfl_xor(half_log_det, o, 32);
-#pragma unroll
-        for (int k = 0; k < BM * MLP_OUT / THREADS; ++k) {
-            const int row = (tid >> 5) + k * (THREADS / 32);
-            const bool in = row < nvalid;
-            const float y = in ? gload1<COH>(out_t, frag_off(row, col)) : 0.0f;                   // mean (cols 0..17), value (col 18)
-            const float a = (in && act) ? act_t[row * MLP_NACT + col] : 0.0f;
-            const float xj = act ? (a - y) * inv_L : 0.0f;
-            float M = xj * xj;
-#pragma unroll
-            for (int o = 1; o < 32; o <<= 1) M += __shfl_xor(M, o, 32);
-            float d = 0.0f, pol = 0.0f, hub = 0.0f;
-            if (in) {
-                const float logp = -0.5f * (33.08178959434617f + M) - half_log_det;
-                const float ratio = expf(logp - olp_t[row]);
-                const float A = adv_t[row];
-                const float s1 = ratio * A;
-                const float rc = fminf(fmaxf(ratio, 1.0f - clip), 1.0f + clip);
-                const float s2 = rc * A;
-                const float in_range = (ratio >= 1.0f - clip && ratio <= 1.0f + clip) ? 1.0f : 0.0f;
-                float dmin;                                    // d min(s1,s2) / d ratio
-                if (s1 < s2) dmin = A;
-                else if (s1 > s2) dmin = A * in_range;
-                else dmin = 0.5f * (A + A * in_range);
-                const float c = -inv_batch * ratio * dmin;     // d loss / d logp
-                pol = -fminf(s1, s2);
-                const float dv = __shfl(y, MLP_NACT, 32) - tgt_t[row];
-                hub = fabsf(dv) < 1.0f ? 0.5f * dv * dv : fabsf(dv) - 0.5f;
-                if (act) d = c * (a - y) * inv_var * elu_grad_from_out(y);
-                else if (col == MLP_NACT) d = inv_batch * fminf(fmaxf(dv, -1.0f), 1.0f);   // smooth_l1', beta = 1
-                dz4_t[frag_off(row, col)] = d;
-            }
-            {
-                u16 sa, sb, sc;
-                split3(d, sa, sb, sc);
-                u16* q = ldsZ4 + row * (MLP_OUT + B3_PAD) + col;
-                q[0] = sa; q[b3_plane<MLP_OUT>()] = sb; q[2 * b3_plane<MLP_OUT>()] = sc;
-            }
-            if (col == 0) { rowloss[2 * row] = pol; rowloss[2 * row + 1] = hub; }
-        }
-    }
-    __syncthreads();
-    if (tid < 32 && loss_part) {       // fixed-order sum of the 32 rows' loss terms
-        float pol = rowloss[2 * tid], hub = rowloss[2 * tid + 1];
-        for (int o = 16; o > 0; o >>= 1) { pol += __shfl_down(pol, o, 32); hub += __shfl_down(hub, o, 32); }
-        if (tid == 0) { loss_part[2 * tile] = pol; loss_part[2 * tile + 1] = hub; }
-    }
+    // loss gradient at the outputs: dZ4 to HBM and to the LDS operand, the tile's loss partials (ends behind its barrier)
+    ppo_loss_phase<COH>(tile, out_saved, action, old_logp, adv, target, var, nvalid, inv_batch, clip, dz4, rowloss, loss_part,
+                        [&](int row, int col, float d) {
+                            u16 sa, sb, sc;
+                            split3(d, sa, sb, sc);
+                            u16* q = ldsZ4 + row * (MLP_OUT + B3_PAD) + col;
+                            q[0] = sa; q[b3_plane<MLP_OUT>()] = sb; q[2 * b3_plane<MLP_OUT>()] = sc;
+                        });
     HFrag<1> hf2;
     {   // dA3 = dZ4 . W4  ->  dZ3
         f32x16 hi, lo;

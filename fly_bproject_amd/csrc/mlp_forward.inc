@@ -230,7 +230,7 @@ __device__ __forceinline__ void forward_body(
 #pragma unroll
                 for (int o = 1; o < 32; o <<= 1) { x2 += __shfl_xor(x2, o, 32); lg += __shfl_xor(lg, o, 32); }
                 if (on) (smp_act + row0 * MLP_NACT)[row * MLP_NACT + col] = fminf(fmaxf(a, -1.0f), 1.0f);
-                if (col == 0 && in) (smp_logp + row0)[row] = -0.5f * (33.08178959434617f + x2) - lg;
+                if (col == 0 && in) (smp_logp + row0)[row] = gauss_logp(x2, lg);
             }
         }
         stamp<STAMP>(stamps, 13);
@@ -492,7 +492,7 @@ __device__ __forceinline__ void forward_body_b3(
                     (smp_act + row0 * MLP_NACT)[row * MLP_NACT + col] = ac;
                     if (act_tile_lds) act_tile_lds[row * MLP_NACT + col] = ac;
                 }
-                if (col == 0 && in) (smp_logp + row0)[row] = -0.5f * (33.08178959434617f + x2) - lg;
+                if (col == 0 && in) (smp_logp + row0)[row] = gauss_logp(x2, lg);
             }
         }
         stamp<STAMP>(stamps, 13);

@@ -13,6 +13,7 @@
 
 namespace {
 
+#include "loss_head.inc"
 #include "mlp_gemm.inc"
 #include "fs_stamp.inc"
 #include "mlp_fused_step.inc"       // constants and helpers only: mlp_fused_step_kernel is instantiated in mlp_mfma.hip

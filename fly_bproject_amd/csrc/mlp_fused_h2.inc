@@ -484,7 +484,8 @@ __global__ __launch_bounds__(THREADS, 1) void mlp_fused_step_h2_kernel(
         __syncthreads();
         stamp<STAMP>(stamps, 6);
         if (!STAMP) fs_split(n);
-        // ---- P5: outputs, loss, dZ4 (ppo.py:184-194): mlp_fused_step.inc's phase on the unscaled sums ------------------------------
+        // ---- P5: outputs, loss, dZ4 (ppo.py:184-194): mlp_fused_step.inc's phase on the unscaled sums; the row's loss is loss_head.inc's
+        //          ppo_row_loss with FAST_EXP (v_exp_f32 on the ratio, ~1 ulp) --------------------------------------------------------
         {
             const float k4 = sc[H2_FSC_INV + H2C_H3] * sc[H2_FSC_INV + H2C_W4], sz4 = sc[H2C_Z4];
             const int c0 = 4 * lq;
@@ -514,26 +515,14 @@ __global__ __launch_bounds__(THREADS, 1) void mlp_fused_step_h2_kernel(
             const float vrow = fs_sum8(lq == MLP_NACT / 4 ? y[MLP_NACT % 4] : 0.0f);
             float d[4] = {0.0f, 0.0f, 0.0f, 0.0f}, pol = 0.0f, hub = 0.0f;
             if (lin) {
-                const float logp = -0.5f * (33.08178959434617f + M) - half_log_det;
-                const float ratio = __expf(logp - l_olp);            // (v_exp_f32: ~1 ulp on the ratio; the bf16x3 kernel keeps expf for bit equality with the three-launch path)
-                const float A = l_adv;
-                const float s1 = ratio * A;
-                const float rc = fminf(fmaxf(ratio, 1.0f - clip), 1.0f + clip);
-                const float s2 = rc * A;
-                const float in_range = (ratio >= 1.0f - clip && ratio <= 1.0f + clip) ? 1.0f : 0.0f;
-                float dmin;
-                if (s1 < s2) dmin = A;
-                else if (s1 > s2) dmin = A * in_range;
-                else dmin = 0.5f * (A + A * in_range);
-                const float c = -inv_batch * ratio * dmin;
-                pol = -fminf(s1, s2);
-                const float dv = vrow - l_tgt;
-                hub = fabsf(dv) < 1.0f ? 0.5f * dv * dv : fabsf(dv) - 0.5f;
+                const PpoRowLoss rl = ppo_row_loss<true>(M, half_log_det, l_olp, l_adv, vrow, l_tgt, inv_batch, clip);
+                pol = rl.pol;
+                hub = rl.hub;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int col = c0 + j;
-                    if (col < MLP_NACT) d[j] = c * (l_a[j] - y[j]) * invV[j] * elu_grad_from_out(y[j]);
-                    else if (col == MLP_NACT) d[j] = inv_batch * fminf(fmaxf(dv, -1.0f), 1.0f);
+                    if (col < MLP_NACT) d[j] = ppo_mean_dz4(rl.c, l_a[j], y[j], invV[j]);
+                    else if (col == MLP_NACT) d[j] = rl.dv;
                     if (DUMP) (dump.dz4 + row0 * MLP_OUT)[frag_off(lrow, col)] = d[j];
                 }
             }
@@ -551,11 +540,7 @@ __global__ __launch_bounds__(THREADS, 1) void mlp_fused_step_h2_kernel(
         fs_tr_init<FS_PX>(trx, lane);
         fs_tr_init<FS_P4>(tr4, lane);
         // ---- P6: dA3 = dZ4 . W4 -> dZ3;  dW4 += dZ4^T H3 ---------------------------------------------------------------
-        if (tl < 32 && loss_part) {
-            float pol = rowloss[2 * tl], hub = rowloss[2 * tl + 1];
-            for (int o = 16; o > 0; o >>= 1) { pol += __shfl_down(pol, o, 32); hub += __shfl_down(hub, o, 32); }
-            if (tl == 0) { loss_part[2 * tile] = pol; loss_part[2 * tile + 1] = hub; }
-        }
+        if (tl < 32 && loss_part) tile_loss_sum<2>(rowloss, tl, loss_part + 2 * tile);
         WeightHead2 wt2;
         {
             f32x16 hi, lo;

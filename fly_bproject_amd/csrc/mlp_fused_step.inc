@@ -504,26 +504,14 @@ __global__ __launch_bounds__(THREADS, 1) void mlp_fused_step_kernel(
             const float vrow = fs_sum8(lq == MLP_NACT / 4 ? y[MLP_NACT % 4] : 0.0f);        // the row's value output (column 18), to all 8 lanes
             float d[4] = {0.0f, 0.0f, 0.0f, 0.0f}, pol = 0.0f, hub = 0.0f;
             if (lin) {
-                const float logp = -0.5f * (33.08178959434617f + M) - half_log_det;
-                const float ratio = expf(logp - l_olp);
-                const float A = l_adv;
-                const float s1 = ratio * A;
-                const float rc = fminf(fmaxf(ratio, 1.0f - clip), 1.0f + clip);
-                const float s2 = rc * A;
-                const float in_range = (ratio >= 1.0f - clip && ratio <= 1.0f + clip) ? 1.0f : 0.0f;
-                float dmin;                                    // d min(s1,s2) / d ratio
-                if (s1 < s2) dmin = A;
-                else if (s1 > s2) dmin = A * in_range;
-                else dmin = 0.5f * (A + A * in_range);
-                const float c = -inv_batch * ratio * dmin;     // d loss / d logp
-                pol = -fminf(s1, s2);
-                const float dv = vrow - l_tgt;
-                hub = fabsf(dv) < 1.0f ? 0.5f * dv * dv : fabsf(dv) - 0.5f;
+                const PpoRowLoss rl = ppo_row_loss<false>(M, half_log_det, l_olp, l_adv, vrow, l_tgt, inv_batch, clip);
+                pol = rl.pol;
+                hub = rl.hub;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int col = c0 + j;
-                    if (col < MLP_NACT) d[j] = c * (l_a[j] - y[j]) * invV[j] * elu_grad_from_out(y[j]);
-                    else if (col == MLP_NACT) d[j] = inv_batch * fminf(fmaxf(dv, -1.0f), 1.0f);   // smooth_l1', beta = 1
+                    if (col < MLP_NACT) d[j] = ppo_mean_dz4(rl.c, l_a[j], y[j], invV[j]);
+                    else if (col == MLP_NACT) d[j] = rl.dv;
                     if (DUMP) (dump.dz4 + row0 * MLP_OUT)[frag_off(lrow, col)] = d[j];
                 }
             }
@@ -540,11 +528,7 @@ __global__ __launch_bounds__(THREADS, 1) void mlp_fused_step_kernel(
         fs_tr_init<FS_PX>(trx, lane);
         fs_tr_init<FS_P4>(tr4, lane);
         // ---- P6: dA3 = dZ4 . W4 -> dZ3;  dW4 += dZ4^T H3 ---------------------------------------------------------------
-        if (tl < 32 && loss_part) {       // fixed-order sum of the 32 rows' loss terms
-            float pol = rowloss[2 * tl], hub = rowloss[2 * tl + 1];
-            for (int o = 16; o > 0; o >>= 1) { pol += __shfl_down(pol, o, 32); hub += __shfl_down(hub, o, 32); }
-            if (tl == 0) { loss_part[2 * tile] = pol; loss_part[2 * tile + 1] = hub; }
-        }
+        if (tl < 32 && loss_part) tile_loss_sum<2>(rowloss, tl, loss_part + 2 * tile);
         WeightHead3 wt2;
         {
             f32x16 hi, lo;
@@ -945,7 +929,7 @@ __device__ __forceinline__ void policy_tile_fs(const FrLds& L, const long tile, 
                     (smp_act + row0 * MLP_NACT)[lrow * MLP_NACT + c0 + j] = ac;
                     L.acts[lrow * MLP_NACT + c0 + j] = ac;
                 }
-            if (lq == 0) (smp_logp + row0)[lrow] = -0.5f * (33.08178959434617f + M) - hld;
+            if (lq == 0) (smp_logp + row0)[lrow] = gauss_logp(M, hld);
         }
     }
     __syncthreads();

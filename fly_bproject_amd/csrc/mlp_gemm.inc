@@ -48,8 +48,6 @@ constexpr int THREADS = 64 * NWAVE;
 // ELU as torch evaluates it: x > 0 ? x : exp(x) - 1 (ELU.cpp), with the hardware exp2 path
 // (v_exp_f32, ~1 ulp on exp): absolute error vs expm1 <= ~1.2e-7, inside the stated 2e-5 tolerance.
 __device__ __forceinline__ float elu(float x) { return x > 0.0f ? x : __expf(x) - 1.0f; }
-// derivative of ELU expressed through its OUTPUT y: 1 for y > 0, y + 1 otherwise
-__device__ __forceinline__ float elu_grad_from_out(float y) { return y > 0.0f ? 1.0f : y + 1.0f; }
 // dA * ELU'(H) with H the saved OUTPUT: ELU' = min(H, 0) + 1, so the product is one min and one fma
 // (dA * min(H, 0) + dA, rounded once) instead of compare, select, add, multiply
 __device__ __forceinline__ float dact(float da, float h) { return fmaf(da, fminf(h, 0.0f), da); }

@@ -36,6 +36,7 @@
 
 namespace {
 
+#include "loss_head.inc"
 #include "mlp_gemm.inc"
 #include "fs_stamp.inc"
 #include "mlp_forward.inc"

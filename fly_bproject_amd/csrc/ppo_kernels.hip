@@ -15,6 +15,8 @@
 
 namespace {
 
+#include "loss_head.inc"
+
 constexpr int NA = FLY_NUM_DOF;
 constexpr int SL_BLOCK = 64;            // rows per workgroup (one wave)
 constexpr int SL_PAD = NA + 1;          // 19-word row pitch: conflict-free column walks
@@ -41,7 +43,7 @@ __global__ __launch_bounds__(SL_BLOCK) void ppo_sample_logprob_kernel(
     float half_log_det = 0.0f;
 #pragma unroll
     for (int j = 0; j < NA; ++j) { L[j] = sqrtf(var[j]); half_log_det = __fadd_rn(half_log_det, logf(L[j])); }
-    const float klog2pi = 33.08178959434617f;   // 18 * log(2*pi)
+    const float klog2pi = GAUSS_DIM_LOG_2PI;    // 18 * log(2*pi)
     if (tid < rows) {
         float M = 0.0f;
 #pragma unroll

@@ -3,15 +3,20 @@
 
     python tools/kernel_resources.py [csv-out]
     python tools/kernel_resources.py --isa-digest [csrc-dir] > digest.txt
+    python tools/kernel_resources.py --isa-histogram before-csrc-dir [csrc-dir]
 
 --isa-digest: one line per kernel, sorted by name -- file, kernel, the figures above, and a SHA-256 of the kernel's disassembled
 body (llvm-objdump -d, addresses and comments stripped) -- so that the device code of two builds (say, before and after a change
 that touches host code only) is compared with `diff`: the order kernels are emitted in does not matter, anything else shows.
 
+--isa-histogram: for every kernel whose disassembled body differs between the two builds, the mnemonics whose counts differ
+(mnemonic before -> after) -- whether a device-code refactor moved arithmetic or only address computation and waits.
+
 For every csrc/*.o: the .hip_fatbin section is unbundled (clang-offload-bundler) and the AMDGPU metadata note of the code
 object read (llvm-readelf --notes): .vgpr_count, .agpr_count, .sgpr_count, .vgpr_spill_count, .sgpr_spill_count,
 .private_segment_fixed_size (scratch bytes per lane), .group_segment_fixed_size (static LDS).  What profiles/README.md quotes.
 """
+import collections
 import glob
 import hashlib
 import os
@@ -81,6 +86,7 @@ def kernels_of(obj, isa=False):
         k["kernel"] = short(dn)
         if isa:
             k["isa"] = hashlib.sha256("\n".join(bodies[k[".name"]]).encode()).hexdigest()
+            k["mnemonics"] = collections.Counter(line.split()[0] for line in bodies[k[".name"]])
     return ks
 
 
@@ -92,9 +98,25 @@ def isa_digest(csrc):
     sys.stdout.write("\n".join(sorted(lines)) + "\n")
 
 
+def isa_histogram(before, after):
+    def load(csrc):
+        return {(os.path.basename(obj)[:-2], k["kernel"].replace(" ", "")): k
+                for obj in sorted(glob.glob(os.path.join(csrc, "*.o"))) for k in kernels_of(obj, isa=True)}
+    a, b = load(before), load(after)
+    for key in sorted(set(a) & set(b)):
+        if a[key]["isa"] != b[key]["isa"]:
+            ma, mb = a[key]["mnemonics"], b[key]["mnemonics"]
+            diff = ["%s %d -> %d" % (m, ma[m], mb[m]) for m in sorted(set(ma) | set(mb)) if ma[m] != mb[m]]
+            print("%s %s: %d -> %d instructions; %s" % (key[0], key[1], sum(ma.values()), sum(mb.values()),
+                                                        ", ".join(diff) or "same mnemonic counts (order / registers only)"))
+
+
 def main():
+    here = os.path.join(REPO, "fly_bproject_amd", "csrc")
     if len(sys.argv) > 1 and sys.argv[1] == "--isa-digest":
-        return isa_digest(sys.argv[2] if len(sys.argv) > 2 else os.path.join(REPO, "fly_bproject_amd", "csrc"))
+        return isa_digest(sys.argv[2] if len(sys.argv) > 2 else here)
+    if len(sys.argv) > 2 and sys.argv[1] == "--isa-histogram":
+        return isa_histogram(sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else here)
     rows = []
     for obj in sorted(glob.glob(os.path.join(REPO, "fly_bproject_amd", "csrc", "*.o"))):
         for k in kernels_of(obj):
