@@ -88,37 +88,77 @@ __global__ __launch_bounds__(ADAM_THREADS) void mlp_adam_apply_kernel(float* __r
     __shared__ float s_wscale[4];
     __shared__ unsigned s_wmax[4];
     const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // step_out != nullptr (data-parallel ranks: the gradient arrives from an all-reduce, nothing has prepared the
     // norm): ONE launch does everything -- every block sums the whole masked gradient itself (297 KB from L2, the
     // same fixed order in every block and on every rank) and the step counter ping-pongs: all blocks read *step,
     // block 0 writes *step_out, so no block can see a counter another block has already advanced.
     const bool self_norm = step_out != nullptr;
-    // fail closed: weights and moments never see an invalid gradient.  `grad_invalid` (optional) is a device word that whoever
-    // produced G sets when G is not what it should be -- dp_allreduce_p2p's err word: ANY of its workgroups that gave up on a
-    // peer sets it, so a gradient that is only PARTLY reduced is refused too (the mark inside G covers only the block that owns it)
-    if (G[MLP_ERR_SLOT] != 0.0f || (grad_invalid && *grad_invalid != 0)) {
-        if (self_norm && blockIdx.x == 0 && tid == 0) *step_out = *step;
-        return;
-    }
-    // this thread's element, requested before the norm is known: the loads fly during the partial sums
+    // ONE memory round trip: every address is known at entry, so everything the launch reads is requested here, before the first
+    // wait -- the words the refusal check needs, the step counter, the fp16x2 bookkeeping, this thread's element with all four
+    // of its destination indices and its layer's weight scale, and its norm partial (self_norm: the first trip of the gradient
+    // sum).  Only stores wait for the check.  (A dead thread of the last block reads element 0: no branch around a load.)
     const int i = blockIdx.x * ADAM_THREADS + tid;
     const bool live = i < MLP_PACKED_FLOATS;
-    const float mk = live ? mask[i] : 0.0f, g_in = live ? G[i] : 0.0f, m_in = live ? m[i] : 0.0f, v_in = live ? v[i] : 0.0f,
-                p_in = live ? P[i] : 0.0f;
-    const int jf = live ? idx_f[i] : -1, jt = live ? idx_t[i] : -1;
-    const int step_now = self_norm ? *step + 1 : *step;     // applied steps once this one is (norm_ready: already advanced)
+    const int ic = live ? i : 0;
+    // An optional buffer that is not passed reads a word of one that is, and the value is dropped: a branch around a load would put
+    // a wait (for its condition, for its kernel argument) between the requests.
+    const int* invalid_p = grad_invalid ? grad_invalid : step;
+    const float* tab = PH ? fsc : norm_ws;
+    const int* ifb = PB ? idx_fb : idx_f;
+    const int* itb = PB ? idx_tb : idx_t;
+    const int layer = ic < MLP_OFF_W2 ? 0 : ic < MLP_OFF_W3 ? 1 : ic < MLP_OFF_W4 ? 2 : 3;
+    const float err_mark = G[MLP_ERR_SLOT];
+    const int invalid_w = *invalid_p, step_in = *step;
+    const float s0 = tab[H2_SINCE], s1 = tab[H2_SINCE + 1];     // (both words: the loads need not wait for *step)
+    const float mk = mask[ic], g_in = G[ic], m_in = m[ic], v_in = v[ic], p_in = P[ic];
+    const int jf_in = idx_f[ic], jt_in = idx_t[ic], kf_in = ifb[ic], kt_in = itb[ic];
+    const float wscale = tab[8 + layer];                        // (a rescale step derives its own below and does not use this)
+    const float part0 = norm_ws[1 + (tid < nparts ? tid : 0)];
+    const float4* g4 = reinterpret_cast<const float4*>(G);
+    const float4* m4 = reinterpret_cast<const float4*>(mask);
+    const int q0 = self_norm ? tid : 0;                         // (the other forms drop it: one line per wave)
+    const float4 ga = g4[q0], ka = m4[q0];
+    const int invalid = grad_invalid ? invalid_w : 0;
+    const int jf = live ? jf_in : -1, jt = live ? jt_in : -1;
+    const int kf = PB ? kf_in : -1, kt = PB ? kt_in : -1;
+    // (the scalar words -- and the kernel arguments only the stores use -- are held to this point, or their requests drift down to
+    // their first use, one round trip each behind a wait)
+    asm volatile("" :: "s"(err_mark), "s"(invalid_w), "s"(step_in), "s"(s0), "s"(s1), "s"(PF), "s"(PT), "s"(PTB), "s"(PTH), "s"(h2_period),
+                 "s"(eps), "s"(max_norm), "s"(part_scale));
+    // bias corrections of torch.optim.Adam, once per workgroup (two powf per thread otherwise): they need the step counter and
+    // nothing else, so lane 0 of waves 1 and 2 works them out, one powf each, side by side, while the element loads are still
+    // in flight and apart from wave 0, which has the norm.  (Only LDS is written: a refused step leaves no trace.)
+    const int step_now = self_norm ? step_in + 1 : step_in;     // applied steps once this one is (norm_ready: already advanced)
+    if (wave == 1 && (tid & 63) == 0) s_step_size = lr / (1.0f - powf(beta1, (float)step_now));
+    if (wave == 2 && (tid & 63) == 0) s_bc2_sqrt = sqrtf(1.0f - powf(beta2, (float)step_now));
+    // the one wait: everything requested above has to have arrived here, so no request can sink below the check
+    asm volatile("" :: "v"(mk), "v"(g_in), "v"(m_in), "v"(v_in), "v"(p_in), "v"(jf_in), "v"(jt_in), "v"(kf_in), "v"(kt_in), "v"(wscale),
+                 "v"(part0), "v"(ga.x), "v"(ka.x));
+    // fail closed: weights and moments never see an invalid gradient.  `grad_invalid` (optional) is a device word that whoever
+    // produced G sets when G is not what it should be -- dp_allreduce_p2p's err word: ANY of its workgroups that gave up on a
+    // peer sets it, so a gradient that is only PARTLY reduced is refused too (the mark inside G covers only the block that owns it).
+    // Nothing has been stored yet.
+    if (err_mark != 0.0f || invalid != 0) {
+        if (self_norm && blockIdx.x == 0 && tid == 0) *step_out = step_in;
+        return;
+    }
     {   // every block re-adds the same partial sums in the same order: identical clip coefficient
         float t = 0.0f;
         if (self_norm) {
-            const float4* g4 = reinterpret_cast<const float4*>(G);
-            const float4* m4 = reinterpret_cast<const float4*>(mask);
-            for (int q = tid; q < MLP_PACKED_FLOATS / 4; q += ADAM_THREADS) {
-                const float4 g = g4[q], k = m4[q];
+            static_assert(MLP_PACKED_FLOATS / 4 >= ADAM_THREADS, "every thread has a first trip");
+            float4 g = ga, k = ka;
+            for (int q = tid;;) {
                 const float a = g.x * grad_scale * k.x, b = g.y * grad_scale * k.y, c = g.z * grad_scale * k.z, d = g.w * grad_scale * k.w;
                 t += (a * a + b * b) + (c * c + d * d);
+                q += ADAM_THREADS;
+                if (q >= MLP_PACKED_FLOATS / 4) break;
+                g = g4[q]; k = m4[q];
             }
-        } else
-        for (int b = tid; b < nparts; b += ADAM_THREADS) t += norm_ws[1 + b];
+        } else {
+            if (tid < nparts) t += part0;
+            for (int b = tid + ADAM_THREADS; b < nparts; b += ADAM_THREADS) t += norm_ws[1 + b];
+        }
         for (int o = 32; o > 0; o >>= 1) t += __shfl_down(t, o, 64);
         if ((tid & 63) == 0) red[tid >> 6] = t;
     }
@@ -133,13 +173,11 @@ __global__ __launch_bounds__(ADAM_THREADS) void mlp_adam_apply_kernel(float* __r
     const int par = step_now & 1;
     bool rescale = false;
     if (PH) {
-        const float s0 = fsc[H2_SINCE], s1 = fsc[H2_SINCE + 1];     // (both words: the loads need not wait for *step)
         const int since = (int)(par ? s0 : s1);
         rescale = since >= h2_period;
         if (blockIdx.x == 0 && tid == 0) fsc[H2_SINCE + par] = rescale ? 1.0f : (float)(since + 1);
     }
-    if (PH && !rescale && tid < 4) s_wscale[tid] = fsc[8 + tid];
-    if (PH && rescale) {
+    if (PH && rescale) {    // (once per h2_period steps: the one dependent load a step may keep, the maxima table)
         if (tid < 4) s_wmax[tid] = 0u;
         __syncthreads();
         float mx[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -174,13 +212,7 @@ __global__ __launch_bounds__(ADAM_THREADS) void mlp_adam_apply_kernel(float* __r
         const float coef = max_norm / (norm + 1e-6f);          // torch.nn.utils.clip_grad_norm_
         s_coef = coef < 1.0f ? coef : 1.0f;
         if (blockIdx.x == 0) norm_ws[0] = norm;
-        // bias corrections of torch.optim.Adam, once per workgroup (two powf per thread otherwise)
         if (self_norm && blockIdx.x == 0) *step_out = step_now;
-        const float ts = (float)step_now;
-        const float bc1 = 1.0f - powf(beta1, ts);
-        const float bc2 = 1.0f - powf(beta2, ts);
-        s_step_size = lr / bc1;
-        s_bc2_sqrt = sqrtf(bc2);
     }
     __syncthreads();
     float p = 0.0f;
@@ -198,18 +230,15 @@ __global__ __launch_bounds__(ADAM_THREADS) void mlp_adam_apply_kernel(float* __r
         // keep the fragment-ordered copies the kernels stream in step with the master weights
         if (jf >= 0) PF[jf] = p;
         if (jt >= 0) PT[jt] = p;
-        int kf = -1, kt = -1;
         if (PB) {       // and the three-term bf16 planes of the bf16x3 GEMM path
             u16 a, b, c;
             split3(p, a, b, c);
-            kf = idx_fb[i]; kt = idx_tb[i];
             if (kf >= 0) { PB[kf] = a; PB[kf + 512] = b; PB[kf + 1024] = c; }
             if (kt >= 0) { PTB[kt] = a; PTB[kt + 512] = b; PTB[kt + 1024] = c; }
         }
         if (PH && kf >= 0) {    // and the two-term fp16 planes of the fp16x2 step (PB's layout with 1024-word blocks instead of 1536), under
             // the layer's scale
-            const int layer = i < MLP_OFF_W2 ? 0 : i < MLP_OFF_W3 ? 1 : i < MLP_OFF_W4 ? 2 : 3;
-            const float ps = p * s_wscale[layer];
+            const float ps = p * (rescale ? s_wscale[layer] : wscale);
             const _Float16 h0 = (_Float16)ps;
             const _Float16 h1 = (_Float16)(ps - (float)h0);
             const u16 a = __builtin_bit_cast(u16, h0), b = __builtin_bit_cast(u16, h1);

@@ -541,6 +541,19 @@ extern "C" hipError_t flyhip_launch_mlp_fused_grad(const float* P, const uint16_
     return hipGetLastError();
 }
 
+// mlp_adam_apply_kernel requests everything it reads at entry, in one round trip (mlp_adam.inc).  What that rests on, held here at
+// compile time: every launch form hands each thread AT MOST ONE norm partial (73 of its own norm kernel, 291 of the slab reductions),
+// so the partial is one of those requests and not a loop behind them; and the words the kernel reads in place of a scale table that
+// is not passed (norm_ws[8 .. 11], norm_ws[H2_SINCE], norm_ws[H2_SINCE + 1]: read and dropped) and every partial lie inside the
+// 1280 floats include/flyhip.h asks of norm_ws.
+constexpr int MLP_NORM_WS_FLOATS = 1280;
+static_assert(ADAM_BLOCKS <= ADAM_THREADS && RED_BLOCKS <= ADAM_THREADS,
+              "one norm partial per thread of mlp_adam_apply_kernel");
+static_assert(1 + ADAM_BLOCKS <= MLP_NORM_WS_FLOATS && 1 + RED_BLOCKS <= MLP_NORM_WS_FLOATS && H2_SINCE + 1 < MLP_NORM_WS_FLOATS &&
+              8 + 3 < MLP_NORM_WS_FLOATS, "mlp_adam_apply_kernel reads norm_ws inside its documented size");
+static_assert(MLP_PACKED_FLOATS / 4 >= ADAM_THREADS && MLP_ERR_SLOT < MLP_PACKED_FLOATS,
+              "the first trip of the self_norm gradient sum and the error mark are inside G");
+
 extern "C" hipError_t flyhip_launch_mlp_adam(float* P, float* PF, float* PT, const int* idx_f, const int* idx_t,
                                              const float* G, const float* mask, float* m,
                                              float* v, int* step, float lr, float beta1, float beta2, float eps,

@@ -469,7 +469,9 @@ int fly_render(FlyHandle h, const float* poses, int32_t frames, const FlyRenderC
  *                     512 and 1024 16-bit words later).  `mask` (packed layout, 0/1)
  *                     freezes padding and structural zeros.  `step` is a device int counter;
  *                     `norm_ws` is a device scratch of >= 1280 floats, norm_ws[0] returns the
- *                     pre-clip gradient norm.  step_out != NULL (data-parallel ranks, the gradient
+ *                     pre-clip gradient norm (the launch requests all it reads at once and, for an
+ *                     optional buffer that is NULL, reads a word of norm_ws / step / idx_frag in its
+ *                     place and drops it: every word of the first 1280 must be readable).  step_out != NULL (data-parallel ranks, the gradient
  *                     comes out of an all-reduce): ONE launch -- every workgroup sums the masked
  *                     gradient itself (norm_ready is ignored) and the counter ping-pongs: *step is
  *                     only read, *step_out = *step + 1 is written; pass the two words alternately.

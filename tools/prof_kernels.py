@@ -3,6 +3,7 @@
 PMC passes).  Usage on the GPU box:
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python3 tools/prof_kernels.py
     rocprofv3 --pmc FETCH_SIZE --output-format csv -d OUT -- python3 tools/prof_kernels.py
+PROF_NORM_READY=1: the optimizer step as the single-rank loop launches it (minibatch_grad(fuse_norm=True) + adam_step(norm_ready=True)).
 """
 import ctypes as C
 import os
@@ -36,9 +37,10 @@ tgt = torch.randn(rows, device="cuda:0")
 var = torch.full((18,), 0.2, device="cuda:0")
 if pol.h2_live():          # the default optimizer step (fp16x2): its scales are measured on the data first, as PPO._update_hip does
     pol.calibrate_h2(x, act, olp, adv, tgt, var, 0.2)
+LOOP_FORM = os.environ.get("PROF_NORM_READY", "0") != "0"   # 1: the single-rank loop's form (the reduction leaves the norm partials)
 for _ in range(REPS):
-    pol.minibatch_grad(x, act, olp, adv, tgt, var, 0.2)
-    pol.adam_step()
+    pol.minibatch_grad(x, act, olp, adv, tgt, var, 0.2, fuse_norm=LOOP_FORM)
+    pol.adam_step(norm_ready=LOOP_FORM)
 if pol.h2_live():
     assert int(pol.h2_overflow.item()) == 0
 xs = torch.randn(N, 73, device="cuda:0")
