@@ -333,6 +333,30 @@ int ppo_td_gae_episodic_vnorm(const float* reward, const float* v, const float* 
     return FLY_OK;
 }
 
+int ppo_minibatch_gather(const float* obs, const float* act, const float* logp, const float* adv, const float* target, int64_t R,
+                         uint32_t seed, uint32_t epoch_key, int64_t first, int64_t n, float* obs_out, float* act_out,
+                         float* logp_out, float* adv_out, float* target_out, int32_t* index_out, void* stream)
+{
+    if (!obs || !act || !logp || !adv || !target || !obs_out || !act_out || !logp_out || !adv_out || !target_out)
+        return fail(FLY_E_ARG, "ppo_minibatch_gather: null pointer");
+    if (R < 1 || R >= (int64_t)1 << 31) return fail(FLY_E_ARG, "ppo_minibatch_gather: R must be in [1, 2^31)");
+    if (n < 1 || first < 0 || first > R - n) return fail(FLY_E_ARG, "ppo_minibatch_gather: [first, first + n) is not a window of [0, R)");
+    if ((reinterpret_cast<uintptr_t>(obs_out) | reinterpret_cast<uintptr_t>(act_out)) & 15)
+        return fail(FLY_E_ARG, "ppo_minibatch_gather: obs_out and act_out must be 16-byte aligned");
+    // an output range that overlaps a source range (what can be seen from here; aliasing is forbidden altogether)
+    const char* src[5] = {(const char*)obs, (const char*)act, (const char*)logp, (const char*)adv, (const char*)target};
+    const char* dst[5] = {(const char*)obs_out, (const char*)act_out, (const char*)logp_out, (const char*)adv_out, (const char*)target_out};
+    const int64_t width[5] = {73 * 4, 18 * 4, 4, 4, 4};
+    for (int d = 0; d < 5; ++d)
+        for (int s = 0; s < 5; ++s)
+            if (dst[d] < src[s] + R * width[s] && src[s] < dst[d] + n * width[d])
+                return fail(FLY_E_ARG, "ppo_minibatch_gather: an output overlaps a source");
+    hipError_t e = flyhip_launch_minibatch_gather(obs, act, logp, adv, target, R, seed, epoch_key, first, n, obs_out, act_out, logp_out,
+                                                  adv_out, target_out, index_out, stream);
+    if (e != hipSuccess) return hip_fail(e, "ppo_minibatch_gather launch");
+    return FLY_OK;
+}
+
 int fly_render(FlyHandle h, const float* poses, int32_t frames, const FlyRenderConfig* rc, uint32_t* rgba_out,
                uint8_t* id_out, void* stream)
 {

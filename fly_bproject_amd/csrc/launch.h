@@ -61,6 +61,12 @@ hipError_t flyhip_launch_td_gae_episodic_vnorm(const float* reward, const float*
                                                const float* table, float gamma, float lambda, int64_t T, int64_t N,
                                                float* target_out, float* adv_out, double* sets, int mode, void* stream);
 
+// minibatch_gather.hip
+hipError_t flyhip_launch_minibatch_gather(const float* obs, const float* act, const float* logp, const float* adv,
+                                          const float* target, int64_t R, uint32_t seed, uint32_t epoch_key, int64_t first,
+                                          int64_t n, float* obs_out, float* act_out, float* logp_out, float* adv_out,
+                                          float* target_out, int32_t* index_out, void* stream);
+
 // mlp_mfma.hip
 hipError_t flyhip_launch_mlp_forward(const float* P, const float* PF, const float* x, int64_t n, float* mu_out, float* v_out,
                                      float* out_save, float* h1_save, float* h2_save, float* h3_save, const uint16_t* PB,

@@ -138,6 +138,9 @@ class PPO:
         self.gae = getattr(args, "gae", "reference")                # read first: a bad value must not leave an env behind
         if self.gae not in ("reference", "episodic"):
             raise ValueError("gae must be reference or episodic (got %r)" % (self.gae,))
+        self.minibatch = getattr(args, "minibatch", "reference")
+        if self.minibatch not in ("reference", "shuffled"):
+            raise ValueError("minibatch must be reference or shuffled (got %r)" % (self.minibatch,))
         self.env = env if env is not None else Fly(args)           # ppo.py:110
         self.num_acts = self.env.num_act
         self.num_obs = self.env.num_obs
@@ -208,6 +211,13 @@ class PPO:
             # the end flags the env carries into the first rollout: its initial reset_buf (every env resets in its first step)
             self._flag_rows()
             self._ended_prev = self.env.reset_buf.clone()
+        # opt-in (`minibatch="shuffled"`): every epoch draws its 15 minibatches from a fresh keyed permutation of ALL T * N rows
+        # of the rollout, gathered into one staging set in front of the unchanged optimizer-step kernels.  NOT
+        # the reference's contiguous-in-time slices (Q3).  Nothing of it goes into a checkpoint: a resumed run counts its
+        # updates, and with them its epoch keys, from 0 again.
+        self._mb_stage = self._mb_index = None
+        if self.minibatch == "shuffled":
+            self._setup_minibatch()
         self._graphs = {}
         self._graphs_form = getattr(self.env, "launch_form", 0)     # the env's kernel selection the captured graphs hold
         self._fwd_args = None
@@ -429,6 +439,56 @@ class PPO:
         self._value_stats.copy_(self._value_stats_next)
         self._value_table.copy_(self._value_table_next)
 
+    # ------------------------------------------------------------------------------------------
+    # shuffled minibatches (opt-in)
+    def _setup_minibatch(self):
+        """The one staging minibatch (obs | action | log-prob | target | advantage rows, 376 B per row: 15.4 MB at the default
+        shape; stream order makes one set enough), this rank's seed (`minibatch_seed`, default `seed`, + rank * 0x9E3779B9
+        wrapping, as domain randomisation) and the count of update() calls the epoch keys are derived from.  Nothing of it goes
+        into a checkpoint: a resumed run counts its updates from 0 again."""
+        dev, rows = self.device, self.mini_chunk_size * int(self.args.num_envs)
+        seed = getattr(self.args, "minibatch_seed", None)
+        if seed is None:
+            seed = getattr(self.args, "seed", 0)
+        self._mb_seed = (int(seed) + int(getattr(self.args, "rank", 0)) * 0x9E3779B9) & 0xFFFFFFFF
+        self._mb_update = 0
+        self._mb_stage = (torch.zeros((rows, self.num_obs), device=dev), torch.zeros((rows, self.num_acts), device=dev),
+                          torch.zeros(rows, device=dev), torch.zeros((rows, 1), device=dev), torch.zeros((rows, 1), device=dev))
+
+    def _gather_minibatch(self, epoch_key, first, rows, obs, action, old_log_prob, target, advantage):
+        """The staged minibatch of positions [first, first + rows) of the permutation (seed, epoch_key) over all T * N rows of
+        what make_data returned: obs [rows, 73], action [rows, 18], old log-prob [rows], target [rows, 1], advantage [rows, 1]
+        -- views of the ONE staging set, valid until the next call (ppo_minibatch_gather, one launch, no host sync).  A pure
+        function of its arguments: a redone optimizer step sees its minibatch again bit for bit.  `_mb_index` (optional int32
+        [rows], tests) receives the source rows."""
+        T, n = self.rollout_size, int(self.args.num_envs)
+        so, sa, sl, st, sv = self._mb_stage
+        p = lambda x: C.c_void_p(x.data_ptr())   # noqa: E731
+        _lib.check(self._lib.ppo_minibatch_gather(
+            p(obs), p(action), p(old_log_prob), p(advantage), p(target), C.c_int64(T * n), C.c_uint32(self._mb_seed),
+            C.c_uint32(epoch_key & 0xFFFFFFFF), C.c_int64(first), C.c_int64(rows), p(so), p(sa), p(sl), p(sv), p(st),
+            p(self._mb_index) if self._mb_index is not None else None, _lib.stream_ptr()), "ppo_minibatch_gather")
+        return so, sa, sl, st, sv
+
+    def _minibatches(self):
+        """The optimizer steps of one update, in order.  reference: (k, j), the rollout's step slices [k, j) of ppo.py:179-181
+        (Q3: the 16th chunk is never visited).  shuffled: (epoch key, window), the same number of steps; epoch e of update u
+        has key u * epoch + e and window w is positions [w * rows, (w + 1) * rows) of its permutation, so each epoch leaves a
+        random sixteenth of the rows out."""
+        mc = self.mini_chunk_size
+        cuts = range(mc, self.rollout_size, mc)
+        if self.minibatch == "shuffled":
+            return [(self._mb_update * self.epoch + e, w) for e in range(self.epoch) for w in range(len(cuts))]
+        return [(j - mc, j) for _ in range(self.epoch) for j in cuts]   # 5 x 15 (Q3)
+
+    def _minibatch(self, item, data):
+        """One entry of _minibatches() as the five tensors of an optimizer step ([mc, N, ..] slices, or the staged rows)."""
+        if self.minibatch == "shuffled":
+            rows = self.mini_chunk_size * int(self.args.num_envs)
+            return self._gather_minibatch(item[0], item[1] * rows, rows, *data)
+        k, j = item
+        return tuple(x[k:j] for x in data)
+
     # ppo.py:230 replaces the whole [T,N,1] buffer by the LAST step's [N,1] mask after every step
     # (Q1).  reset_buf only changes inside env.step, so deriving the mask on demand is the same
     # thing without two tiny launches per step; an explicit assignment (tests) overrides it.
@@ -582,7 +642,8 @@ class PPO:
 
     def update(self):
         """ppo.py:173-202: 5 epochs x 15 contiguous-in-T minibatches; the 16th chunk is never
-        visited (Q3).  With world_size > 1 the flat gradient is all-reduced (mean) before the clip."""
+        visited (Q3).  With world_size > 1 the flat gradient is all-reduced (mean) before the clip.
+        minibatch='shuffled': the same 75 steps on windows of a fresh permutation of all rows per epoch."""
         if getattr(self, "_book_terms", None) is not None:
             self._flush_bookkeeping()                               # the loss uses the variance after this rollout's decays
         obs, action, old_log_prob, target, advantage = self.make_data()
@@ -590,48 +651,48 @@ class PPO:
             self._update_hip(obs, action, old_log_prob, target, advantage)
         else:
             self._update_torch(obs, action, old_log_prob, target, advantage)
+        if self.minibatch == "shuffled":
+            self._mb_update += 1                                    # the next update's epoch keys
         if self.normalize_obs:
             self._merge_obs_stats()                                 # after update k: the statistics of rollout k + 1
         if self.normalize_value:
             self._commit_value_stats()                              # after update k: the table make_data k + 1 denormalises with
 
     def _update_torch(self, obs, action, old_log_prob, target, advantage):
-        for _ in range(self.epoch):
-            k = 0
-            for j in range(self.mini_chunk_size, self.rollout_size, self.mini_chunk_size):
-                loss = self.minibatch_loss(obs[k:j], action[k:j], old_log_prob[k:j], target[k:j], advantage[k:j])
-                if self._flat_grad is not None:
-                    self._flat_grad.zero()                          # grads are views of the flat buffer
-                else:
-                    self.optim.zero_grad()
-                loss.backward()
-                if self._flat_grad is not None:
-                    self._flat_grad.allreduce_mean()
-                nn.utils.clip_grad_norm_(self.net.parameters(), 1.0)
-                self.optim.step()
-                self.optim_step += 1
-                k = j
+        data = (obs, action, old_log_prob, target, advantage)
+        for item in self._minibatches():
+            loss = self.minibatch_loss(*self._minibatch(item, data))
+            if self._flat_grad is not None:
+                self._flat_grad.zero()                              # grads are views of the flat buffer
+            else:
+                self.optim.zero_grad()
+            loss.backward()
+            if self._flat_grad is not None:
+                self._flat_grad.allreduce_mean()
+            nn.utils.clip_grad_norm_(self.net.parameters(), 1.0)
+            self.optim.step()
+            self.optim_step += 1
         self.policy.refresh()       # torch wrote the master weights: rebuild the fragment-ordered copies
 
     def _update_hip(self, obs, action, old_log_prob, target, advantage):
         """ppo.py:179-202 on the MFMA kernels: per minibatch one fused forward, the loss gradient +
         dX chain, the split-row dW, (world_size > 1: ONE all-reduce of the packed gradient), and
         the fused clip + Adam step.  Minibatches are contiguous slices of the rollout, so no
-        gather/copy happens."""
+        gather/copy happens -- except with minibatch='shuffled', where one gather launch stages each step's rows."""
         import torch.distributed as dist
-        mc, n = self.mini_chunk_size, int(self.args.num_envs)
-        rows = mc * n
+        rows = self.mini_chunk_size * int(self.args.num_envs)
         pol = self.policy
         sync_grads = self.world_size > 1 and self.dp_mode == "grad_allreduce"
-        slices = [(j - mc, j) for _ in range(self.epoch) for j in range(mc, self.rollout_size, mc)]   # 5 x 15 (Q3)
+        slices = self._minibatches()     # reference: 5 x 15 (k, j) step slices (Q3); shuffled: 5 x 15 (epoch key, window)
+        data = (obs, action, old_log_prob, target, advantage)
         self.prepare()                   # idempotent; callers that time the update call it themselves before warm-up
 
         def run(todo):
-            for k, j in todo:
-                pol.minibatch_grad(obs[k:j].view(rows, self.num_obs), action[k:j].view(rows, self.num_acts),
-                                   old_log_prob[k:j].view(rows), advantage[k:j].view(rows),
-                                   target[k:j].view(rows), self._action_var, self.clip,
-                                   fuse_norm=not sync_grads)
+            for item in todo:
+                # shuffled: the rows are staged again from (epoch key, window), so a redone step sees its minibatch bit for bit
+                o, a, lp, tg, adv = self._minibatch(item, data)
+                pol.minibatch_grad(o.view(rows, self.num_obs), a.view(rows, self.num_acts), lp.view(rows), adv.view(rows),
+                                   tg.view(rows), self._action_var, self.clip, fuse_norm=not sync_grads)
                 if sync_grads:
                     if self._p2p is not None:
                         self._p2p.allreduce_(pol.G)                 # one launch, one xGMI hop, sum in rank order
@@ -646,9 +707,9 @@ class PPO:
         if pol.h2_live() and pol.fused_step and not pol.h2_calibrated:
             # fp16x2 step: the per-class scales are measured on the first minibatch before anything depends on them (a new
             # network, or an update whose values outgrew the scales: a few discarded launches, host-synchronising, rare)
-            k, j = slices[0]
-            pol.calibrate_h2(obs[k:j].view(rows, self.num_obs), action[k:j].view(rows, self.num_acts), old_log_prob[k:j].view(rows),
-                             advantage[k:j].view(rows), target[k:j].view(rows), self._action_var, self.clip)
+            o, a, lp, tg, adv = self._minibatch(slices[0], data)
+            pol.calibrate_h2(o.view(rows, self.num_obs), a.view(rows, self.num_acts), lp.view(rows), adv.view(rows),
+                             tg.view(rows), self._action_var, self.clip)
         run(slices)
         if self._p2p is not None and not self._p2p.check():
             # FIRST, before anything looks at the step counter: a bounded wait of the peer-to-peer exchange expired on this

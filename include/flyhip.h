@@ -271,6 +271,29 @@ int ppo_td_gae_episodic_vnorm(const float* reward, const float* v, const float* 
                               float gamma, float lambda, int64_t T, int64_t N, float* target_out, float* adv_out, double* sets,
                               int mode_flags, void* stream);
 
+/* Shuffled PPO minibatches (opt-in, PPO --minibatch shuffled).  NOT the reference's minibatches
+ * (ppo.py:173-202: contiguous slices of the rollout in time order).  A minibatch is a window of a keyed permutation pi of the
+ * rollout's R rows, gathered into contiguous staging tensors in front of the unchanged optimizer-step kernels.  pi is a pure
+ * function of (seed, epoch_key, position), evaluated in the kernel: a balanced 6-round Feistel network with cycle walking, all
+ * arithmetic uint32 and wrapping, lowbias32 as below (domain randomisation):
+ *     b = max(2, bit_length(R - 1)) rounded up to even;  h = b / 2;  mask = 2^h - 1
+ *     key = lowbias32(seed ^ lowbias32(epoch_key))
+ *     x = i
+ *     repeat:  L = x >> h;  Q = x & mask
+ *              for r = 0 .. 5:  f = lowbias32(Q + key + 0x9E3779B9 * (r + 1)) & mask;  (L, Q) = (Q, L ^ f)
+ *              x = (L << h) | Q
+ *     until x < R;   pi(i) = x
+ *   A bijection of [0, R) by construction; the domain is below 4 R, so a position walks fewer than 4 times on average.
+ * ppo_minibatch_gather: output row k (0 <= k < n) is source row pi(first + k) of obs f32 [R][73], act f32 [R][18] and
+ *   logp / adv / target f32 [R]: a bitwise copy (NaN payloads, infinities and -0 pass through).  index_out (optional int32 [n])
+ *   receives pi(first + k).  Sources need 4-byte alignment only (rollout views); obs_out and act_out must be 16-byte aligned.
+ *   Outputs must not alias or overlap any source: an overlap of the ranges is FLY_E_ARG, anything subtler is undefined.
+ *   FLY_E_ARG also for a null required pointer, R < 1, R >= 2^31, n < 1, first < 0 and first + n > R; nothing is written then.
+ *   Deterministic (one writer per output word, no atomics), graph-capturable, no host sync. */
+int ppo_minibatch_gather(const float* obs, const float* act, const float* logp, const float* adv, const float* target, int64_t R,
+                         uint32_t seed, uint32_t epoch_key, int64_t first, int64_t n, float* obs_out, float* act_out,
+                         float* logp_out, float* adv_out, float* target_out, int32_t* index_out, void* stream);
+
 /* Per-env physics domain randomisation (opt-in).  The reference has none: every env of a batch runs
  * the one parameter set of the config.  With a table registered, env e runs FlyDyn on its own constants
  *     kp * m0, kd * m1, effort * m2, mass * m3 and inertia[i] * m3, mu * m4, gravity * m5   (fp32, rounded once each)

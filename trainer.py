@@ -14,6 +14,10 @@ outputs are mapped back to reward units wherever they meet rewards; the statisti
 value_rms.* and loaded with it; such a checkpoint needs `--normalize_value` to load.
 `--gae episodic` (episode-aware advantage estimate with time-limit bootstrapping; the default `reference` is
 the reference's estimator with its quirks).
+`--minibatch shuffled` (every epoch draws its 15 minibatches from a fresh permutation of ALL rows of the rollout, DESIGN.md
+3.3e; the default `reference` is the reference's 15 contiguous-in-time slices, the same in every epoch, the 16th chunk never
+visited) with `--minibatch_seed` (default `--seed`; rank r adds r * 0x9E3779B9).  The permutation is a pure function of the seed,
+the count of updates and the epoch: nothing of it goes into the checkpoint, and a resumed run counts its updates from 0 again.
 `--randomize` (per-env physics domain randomisation, off by default): each env runs on its own multipliers of kp, kd, effort,
 mass (and inertia), mu and gravity, drawn from `--dr_<name> LO HI` at every reset of that env with seed `--dr_seed` (default
 `--seed`; rank r adds r * 0x9E3779B9).  A property of the env: nothing of it goes into the checkpoint.
@@ -79,6 +83,12 @@ def parse_args(argv=None):
                              'recurrence stops at every episode end, time-outs bootstrap from the value of the next observation '
                              '(rl_games value_bootstrap / time_outs) and the step that performs a reset trains nothing.  episodic '
                              'is NOT the reference\'s estimator; off by default')
+    parser.add_argument('--minibatch', type=str, default="reference", choices=["reference", "shuffled"],
+                        help='minibatches of the update: reference = ppo.py:173-202 as it stands (15 contiguous-in-time slices of the '
+                             'rollout, the same in every epoch; the 16th chunk trains nothing); shuffled = every epoch cuts its 15 '
+                             'minibatches from a fresh keyed permutation of all rows of the rollout (still 75 optimizer steps per '
+                             'update; each epoch leaves a random sixteenth out).  shuffled is NOT the reference\'s update; off by default')
+    parser.add_argument('--minibatch_seed', type=int, default=None, help='seed of the minibatch permutations (default: --seed)')
     parser.add_argument('--obs_clip', type=float, default=5.0, help='bound of a normalised observation (with --normalize_obs)')
     parser.add_argument('--randomize', action='store_true',
                         help='per-env physics domain randomisation, redrawn at every reset of the env (Isaac Gym actor-property '
