@@ -65,6 +65,7 @@ SYMBOLS = {
     "ppo_td_gae_episodic": [_P, _P, _P, _P, _P, _P, _L, _F, _F, _L, _L, _P, _P, _I, _P],
     "ppo_td_gae_episodic_vnorm": [_P, _P, _P, _P, _P, _P, _L, _P, _F, _F, _L, _L, _P, _P, _P, _I, _P],
     "ppo_minibatch_gather": [_P] * 5 + [_L, C.c_uint32, C.c_uint32, _L, _L] + [_P] * 6 + [_P],
+    "ppo_noise_ar1": [_P, _P, _L, _L, _F, _P],
     "ppo_step_bookkeeping": [_P, _L, _P, _F, _P, _I, _F, _F, _P],
     "ppo_rollout_step": [_P, _P, _P, _P, _P, _P, _P, _I, _F, _F, _P, _P, _P, _P, _P, _P],
     "ppo_rollout_all": [_P, _P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],

@@ -357,6 +357,16 @@ int ppo_minibatch_gather(const float* obs, const float* act, const float* logp, 
     return FLY_OK;
 }
 
+int ppo_noise_ar1(float* eps, float* carry, int64_t T, int64_t C, float rho, void* stream)
+{
+    if (!eps || !carry) return fail(FLY_E_ARG, "ppo_noise_ar1: null pointer");
+    if (T <= 0 || C <= 0) return fail(FLY_E_ARG, "ppo_noise_ar1: T and C must be > 0");
+    if (!(rho > 0.0f && rho < 1.0f)) return fail(FLY_E_ARG, "ppo_noise_ar1: rho must be in (0, 1) (got %g)", (double)rho);   // NaN too
+    hipError_t e = flyhip_launch_noise_ar1(eps, carry, T, C, rho, stream);
+    if (e != hipSuccess) return hip_fail(e, "ppo_noise_ar1 launch");
+    return FLY_OK;
+}
+
 int fly_render(FlyHandle h, const float* poses, int32_t frames, const FlyRenderConfig* rc, uint32_t* rgba_out,
                uint8_t* id_out, void* stream)
 {

@@ -67,6 +67,9 @@ hipError_t flyhip_launch_minibatch_gather(const float* obs, const float* act, co
                                           int64_t n, float* obs_out, float* act_out, float* logp_out, float* adv_out,
                                           float* target_out, int32_t* index_out, void* stream);
 
+// noise_ar1.hip
+hipError_t flyhip_launch_noise_ar1(float* eps, float* carry, int64_t T, int64_t C, float rho, void* stream);
+
 // mlp_mfma.hip
 hipError_t flyhip_launch_mlp_forward(const float* P, const float* PF, const float* x, int64_t n, float* mu_out, float* v_out,
                                      float* out_save, float* h1_save, float* h2_save, float* h3_save, const uint16_t* PB,

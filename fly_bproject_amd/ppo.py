@@ -141,6 +141,12 @@ class PPO:
         self.minibatch = getattr(args, "minibatch", "reference")
         if self.minibatch not in ("reference", "shuffled"):
             raise ValueError("minibatch must be reference or shuffled (got %r)" % (self.minibatch,))
+        self.action_noise = getattr(args, "action_noise", "white")
+        if self.action_noise not in ("white", "ar1"):
+            raise ValueError("action_noise must be white or ar1 (got %r)" % (self.action_noise,))
+        self.noise_rho = float(getattr(args, "noise_rho", 0.5))
+        if not 0.0 < self.noise_rho < 1.0:
+            raise ValueError("noise_rho must be in (0, 1) (got %r)" % (self.noise_rho,))
         self.env = env if env is not None else Fly(args)           # ppo.py:110
         self.num_acts = self.env.num_act
         self.num_obs = self.env.num_obs
@@ -218,6 +224,13 @@ class PPO:
         self._mb_stage = self._mb_index = None
         if self.minibatch == "shuffled":
             self._setup_minibatch()
+        # opt-in (`action_noise="ar1"`): the rollout's noise is an AR(1) process along time with unit stationary variance, made
+        # by one filter launch over `_eps_all` right behind the white draw.  NOT the reference's sampling.  The
+        # carry [N, 18] is the process' last row: drawn once before the first rollout (`_draw_noise`), then handed from rollout
+        # to rollout by the launch.  Nothing of it goes into a checkpoint or to another rank.
+        self._noise_carry, self._noise_carry_drawn = None, False
+        if self.action_noise == "ar1":
+            self._noise_carry = torch.zeros((n, self.num_acts), device=dev)
         self._graphs = {}
         self._graphs_form = getattr(self.env, "launch_form", 0)     # the env's kernel selection the captured graphs hold
         self._fwd_args = None
@@ -885,6 +898,21 @@ class PPO:
             raise _lib.FlyHipError("normalize_obs: the two-launch rollout step (FLY_FUSE_ROLLOUT_STEP=0, mlp_forward_sample) does not "
                                    "normalise observations; use the one-launch step")
 
+    def _draw_noise(self):
+        """The noise of a whole rollout into `_eps_all` [T, N, 18], on the current stream (captured with the rollout in a graph).
+        white: one normal_() and nothing else.  ar1: the same draw, then ppo_noise_ar1 filters it in place along time from the
+        carry, so `_eps_all` holds what the rollout uses; the carry is drawn from the stationary law immediately before the
+        first rollout's draw (the first rollout always runs eagerly) and left to the launches after that."""
+        if self.action_noise == "ar1" and not self._noise_carry_drawn:
+            self._noise_carry.normal_(generator=self._gen)
+            self._noise_carry_drawn = True
+        self._eps_all.normal_(generator=self._gen)
+        if self.action_noise == "ar1":
+            T, n = self.rollout_size, int(self.args.num_envs)
+            _lib.check(self._lib.ppo_noise_ar1(
+                C.c_void_p(self._eps_all.data_ptr()), C.c_void_p(self._noise_carry.data_ptr()), C.c_int64(T),
+                C.c_int64(n * self.num_acts), C.c_float(self.noise_rho), _lib.stream_ptr()), "ppo_noise_ar1")
+
     def _launch_step(self, t):
         """The device work of one env step (ppo.py:213-237): ONE launch (`ppo_rollout_step`), no host logic.  Rows of
         the rollout are written in place (obs row t+1, action/log-prob/reward rows t); the score and
@@ -892,7 +920,7 @@ class PPO:
         lib, env = self._lib, self.env
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         if t == 0:
-            self._eps_all.normal_(generator=self._gen)              # the eps of MultivariateNormal.sample, whole rollout
+            self._draw_noise()                                      # the eps of MultivariateNormal.sample, whole rollout
             self._rows_applied.zero_()                              # a new rollout: no row's bookkeeping applied yet
         env.obs_buf, env.reward_buf = self._obs_rows[t + 1], self._reward_rows[t]      # ppo.py:228-229
         env._bufs.obs, env._bufs.reward = self._buf_ptrs[t]
@@ -920,7 +948,7 @@ class PPO:
         the T steps of its own 32 envs with the env state in registers.  Bit for bit what T `_launch_step` calls leave."""
         P = C.c_void_p
         pol, env, T = self.policy, self.env, self.rollout_size
-        self._eps_all.normal_(generator=self._gen)
+        self._draw_noise()
         self._rows_applied.zero_()
         self._flag_rows()
         if self.gae == "episodic":

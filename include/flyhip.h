@@ -294,6 +294,24 @@ int ppo_minibatch_gather(const float* obs, const float* act, const float* logp, 
                          uint32_t seed, uint32_t epoch_key, int64_t first, int64_t n, float* obs_out, float* act_out,
                          float* logp_out, float* adv_out, float* target_out, int32_t* index_out, void* stream);
 
+/* Temporally correlated exploration noise (opt-in, PPO --action_noise ar1).  NOT the reference's
+ * sampling (ppo.py:215-220 draws white noise at every step).  AR(1) noise with unit stationary variance along the time axis of
+ * the rollout's noise buffer eps f32 [T][C] (C = 18 N), per column c, in place: x is what the buffer holds on entry (the white
+ * draw), y what it holds on return.  All ops fp32 and separately rounded (no fma), s formed in double and rounded once:
+ *     s        = (float) sqrt(1.0 - (double) rho * (double) rho)
+ *     y[-1][c] = carry[c]
+ *     y[t][c]  = fadd(fmul(rho, y[t-1][c]), fmul(s, x[t][c]))          t = 0 .. T-1
+ *     carry[c] = y[T-1][c]                                              written by the same launch
+ *   With carry ~ N(0,1) and x ~ N(0,1) i.i.d. every y[t] is N(0,1) and corr(y[t], y[t+k]) = rho^k: each step's noise is still a
+ *   standard normal marginally, so the log-prob the sampling epilogues store is still the density of the action under
+ *   N(mu, var).  The carry makes consecutive calls one continuous process.  The process is NOT restarted at episode ends:
+ *   resets happen inside the rollout launch and are not known when the noise is made.
+ * ppo_noise_ar1: carry f32 [C] is read and rewritten.  eps and carry need 4-byte alignment only; wider accesses are used where
+ *   C and both bases allow, with the same bits.  A NaN or an infinity stays in its column.  FLY_E_ARG for a null pointer, T < 1,
+ *   C < 1 and unless 0 < rho < 1 (a NaN rho included); nothing is written then.  eps and carry must not overlap.
+ *   Deterministic (one writer per word, no atomics), graph-capturable, no host sync. */
+int ppo_noise_ar1(float* eps, float* carry, int64_t T, int64_t C, float rho, void* stream);
+
 /* Per-env physics domain randomisation (opt-in).  The reference has none: every env of a batch runs
  * the one parameter set of the config.  With a table registered, env e runs FlyDyn on its own constants
  *     kp * m0, kd * m1, effort * m2, mass * m3 and inertia[i] * m3, mu * m4, gravity * m5   (fp32, rounded once each)

@@ -18,6 +18,10 @@ the reference's estimator with its quirks).
 3.3e; the default `reference` is the reference's 15 contiguous-in-time slices, the same in every epoch, the 16th chunk never
 visited) with `--minibatch_seed` (default `--seed`; rank r adds r * 0x9E3779B9).  The permutation is a pure function of the seed,
 the count of updates and the epoch: nothing of it goes into the checkpoint, and a resumed run counts its updates from 0 again.
+`--action_noise ar1` (temporally correlated exploration noise, DESIGN.md 3.2b: the rollout's noise is an AR(1) process along
+time with unit stationary variance and lag-1 correlation `--noise_rho`, default 0.5; the default `white` is the reference's
+independent draw at every step).  Each step's noise is still N(0, 1), so the stored log-probs stay the densities of the actions.
+The process runs on from rollout to rollout and is not restarted at episode ends; nothing of it goes into the checkpoint.
 `--randomize` (per-env physics domain randomisation, off by default): each env runs on its own multipliers of kp, kd, effort,
 mass (and inertia), mu and gravity, drawn from `--dr_<name> LO HI` at every reset of that env with seed `--dr_seed` (default
 `--seed`; rank r adds r * 0x9E3779B9).  A property of the env: nothing of it goes into the checkpoint.
@@ -89,6 +93,14 @@ def parse_args(argv=None):
                              'minibatches from a fresh keyed permutation of all rows of the rollout (still 75 optimizer steps per '
                              'update; each epoch leaves a random sixteenth out).  shuffled is NOT the reference\'s update; off by default')
     parser.add_argument('--minibatch_seed', type=int, default=None, help='seed of the minibatch permutations (default: --seed)')
+    parser.add_argument('--action_noise', type=str, default="white", choices=["white", "ar1"],
+                        help='exploration noise of the rollout: white = ppo.py:215-220 as it stands (an independent N(0, 1) draw per '
+                             'step and joint); ar1 = the draws of a rollout are filtered along time into an AR(1) process with unit '
+                             'stationary variance (each step still N(0, 1), corr(t, t + k) = rho^k; continuous across rollouts, not '
+                             'restarted at episode ends).  ar1 is NOT the reference\'s sampling; off by default')
+    parser.add_argument('--noise_rho', type=float, default=0.5,
+                        help='lag-1 correlation of --action_noise ar1, 0 < rho < 1 (0.5: between white and pink noise, a starting '
+                             'choice, not a measurement)')
     parser.add_argument('--obs_clip', type=float, default=5.0, help='bound of a normalised observation (with --normalize_obs)')
     parser.add_argument('--randomize', action='store_true',
                         help='per-env physics domain randomisation, redrawn at every reset of the env (Isaac Gym actor-property '
