@@ -176,6 +176,7 @@ class PackedPolicy:
         self.h2_calibrated = False
         self.h2_suspended = False           # True while refused steps are redone on the bf16x3 kernel (the planes stay maintained)
         self.h2_overflows = 0               # updates in which the fp16x2 step was refused and redone on bf16x3
+        self.h2_calibration_failures = 0    # data-parallel updates run on bf16x3 because some rank's calibrate_h2 did not settle
         self._h2_reset_scales()
         idx_fb, idx_tb = build_plane_maps()
         self.idx_fb = torch.from_numpy(idx_fb).to(self.device)

@@ -687,6 +687,24 @@ class PPO:
             self.optim_step += 1
         self.policy.refresh()       # torch wrote the master weights: rebuild the fragment-ordered copies
 
+    def _optimizer_step(self, obs, action, old_log_prob, advantage, target, sync_grads):
+        """One optimizer step of `_update_hip` on this rank's rows (flat: obs [rows, 73], action [rows, 18], the rest [rows]):
+        the gradient launch, with `sync_grads` the exchange of the packed gradient, and the clip + Adam launch.  Each rank
+        divides by ITS row count and the launch scales the summed gradient by 1 / world_size: the mean over the global
+        minibatch, which the clip then sees (tests/test_dist_step_gpu.py holds two ranks of this to float64)."""
+        pol = self.policy
+        pol.minibatch_grad(obs, action, old_log_prob, advantage, target, self._action_var, self.clip, fuse_norm=not sync_grads)
+        if sync_grads:
+            if self._p2p is not None:
+                self._p2p.allreduce_(pol.G)                 # one launch, one xGMI hop, sum in rank order
+            else:
+                import torch.distributed as dist
+                dist.all_reduce(pol.G, op=dist.ReduceOp.SUM)    # 297 KB, latency-bound on xGMI
+        # either way ONE optimizer launch per step; it reads the exchange's err word itself and refuses a gradient
+        # that ANY workgroup of the exchange left un-reduced (fail closed, on the device)
+        pol.adam_step(grad_scale=1.0 / self.world_size if sync_grads else 1.0, norm_ready=not sync_grads,
+                      self_norm=sync_grads, grad_invalid=self._p2p.err if (sync_grads and self._p2p is not None) else None)
+
     def _update_hip(self, obs, action, old_log_prob, target, advantage):
         """ppo.py:179-202 on the MFMA kernels: per minibatch one fused forward, the loss gradient +
         dX chain, the split-row dW, (world_size > 1: ONE all-reduce of the packed gradient), and
@@ -704,25 +722,37 @@ class PPO:
             for item in todo:
                 # shuffled: the rows are staged again from (epoch key, window), so a redone step sees its minibatch bit for bit
                 o, a, lp, tg, adv = self._minibatch(item, data)
-                pol.minibatch_grad(o.view(rows, self.num_obs), a.view(rows, self.num_acts), lp.view(rows), adv.view(rows),
-                                   tg.view(rows), self._action_var, self.clip, fuse_norm=not sync_grads)
-                if sync_grads:
-                    if self._p2p is not None:
-                        self._p2p.allreduce_(pol.G)                 # one launch, one xGMI hop, sum in rank order
-                    else:
-                        dist.all_reduce(pol.G, op=dist.ReduceOp.SUM)    # 297 KB, latency-bound on xGMI
-                # either way ONE optimizer launch per step; it reads the exchange's err word itself and refuses a gradient
-                # that ANY workgroup of the exchange left un-reduced (fail closed, on the device)
-                pol.adam_step(grad_scale=1.0 / self.world_size if sync_grads else 1.0, norm_ready=not sync_grads,
-                              self_norm=sync_grads, grad_invalid=self._p2p.err if (sync_grads and self._p2p is not None) else None)
+                self._optimizer_step(o.view(rows, self.num_obs), a.view(rows, self.num_acts), lp.view(rows), adv.view(rows),
+                                     tg.view(rows), sync_grads)
 
         self._check_step_counter()       # the previous update's counter, copied while this rollout ran
+        cal_failed = False
         if pol.h2_live() and pol.fused_step and not pol.h2_calibrated:
             # fp16x2 step: the per-class scales are measured on the first minibatch before anything depends on them (a new
             # network, or an update whose values outgrew the scales: a few discarded launches, host-synchronising, rare)
             o, a, lp, tg, adv = self._minibatch(slices[0], data)
-            pol.calibrate_h2(o.view(rows, self.num_obs), a.view(rows, self.num_acts), lp.view(rows), adv.view(rows),
-                             tg.view(rows), self._action_var, self.clip)
+            failed = None
+            try:
+                pol.calibrate_h2(o.view(rows, self.num_obs), a.view(rows, self.num_acts), lp.view(rows), adv.view(rows),
+                                 tg.view(rows), self._action_var, self.clip)
+            except _lib.FlyHipError as e:
+                if not sync_grads:
+                    raise                # one rank, or param_average (no exchange inside the update for a peer to wait in)
+                failed = e
+            if sync_grads:
+                # The ranks calibrate on their own rows, so one of them may fail to settle where its peers succeed -- and a rank
+                # that raised here would leave them waiting in the update's first all-reduce.  So the verdict is the ranks'
+                # together: ONE status word (MAX) over the process group, exchanged only when a calibration was attempted --
+                # which every rank decides alike (`h2_calibrated` starts False everywhere and flips only on refusals every rank
+                # sees).  If any rank failed, EVERY rank runs this update on bf16x3 and calibrates again at the next one.
+                word = torch.tensor([0 if failed is None else 1], dtype=torch.int32, device=self.device)
+                dist.all_reduce(word, op=dist.ReduceOp.MAX)
+                if int(word.item()) != 0:
+                    if failed is not None:
+                        print("rank %d: %s; every rank runs this update on bf16x3" % (int(getattr(self.args, "rank", 0)), failed))
+                    pol.h2_suspended = cal_failed = True        # cleared at the end of this update, below
+                    pol.h2_calibrated = False
+                    pol.h2_calibration_failures += 1
         run(slices)
         if self._p2p is not None and not self._p2p.check():
             # FIRST, before anything looks at the step counter: a bounded wait of the peer-to-peer exchange expired on this
@@ -748,6 +778,8 @@ class PPO:
                     raise _lib.FlyHipError("update: the device step counter says %d optimizer steps, %d were issued"
                                            % (got, pol.steps_issued))
                 self._drain_log(block=True)
+            if cal_failed:
+                pol.h2_suspended = False
             self.optim_step += len(slices)
             self._finish_update(sync_grads)
             return
