@@ -346,6 +346,79 @@ def test_fused_equals_unfused_bit_exact():
     fused.exit(); split.exit()
 
 
+def death_seed_state(cfg, n):
+    """A first state from which every way of ending an episode occurs within a few steps: the start pose (one oracle step
+    from the all-flagged initial state), then a few envs moved above termination_height_up, a few below termination_height,
+    a few rolled by 120 degrees (qz^2 + qw^2 = 0.25 < 0.5), a few pitched nose-up by 60 degrees at z = 1.5 (qz^2 + qw^2 = 0.75:
+    alive, with the abdomen's tail under the ground: abdomen contact in the first step, in either gravity), one at
+    progress = max - 3.  Envs 0..7 are the fallers (the caller drives every joint of theirs to its upper limit)."""
+    s = O.EnvState(n)
+    s.root[:, 2], s.root[:, 6] = cfg.start_height, 1.0   # (lowGrav integrates before it resets: give it a pose to integrate)
+    s.dof_pos[:] = np.array(cfg.dof_pose[:], np.float32)
+    O.env_step(cfg, s, pose_actions(cfg, n))
+    assert not s.reset.any() and np.isfinite(s.contact).all()
+    s.root[10:14, 2] = 20.0
+    s.root[14:18, 2] = np.array([0.9, 0.3, 1.0, 0.6], np.float32)
+    s.root[14:18, 7:] = 0.0
+    s.root[18:22, 3:7] = np.array([np.sin(np.pi / 3), 0.0, 0.0, np.cos(np.pi / 3)], np.float32)
+    s.root[22:26, 2] = 1.5
+    s.root[22:26, 3:7] = np.array([0.0, -0.5, 0.0, np.sqrt(0.75)], np.float32)
+    s.root[22:26, 7:] = 0.0
+    s.progress[30] = cfg.max_episode_length - 3
+    return s
+
+
+@pytest.mark.parametrize("variant", ["bigGrav", "lowGrav"])
+def test_fused_equals_unfused_bit_exact_through_deaths(variant):
+    """The fused launch against the split launches where envs DIE: the `dead` and time-limit branches of the fused
+    instantiation, in both variants' order (reset before `simulate`, or after it with reset_after_sim).  The fused env runs
+    freely for 60 steps from death_seed_state; before each step its state is pushed to the split env, after it all eleven
+    buffers are compared bit for bit.  Each way of ending an episode must occur, classified from the post-step buffers
+    with the numpy reference of tests/env_pack_ref.py (which the fused done mask must equal on every row, too): above
+    termination_height_up, below termination_height, tilted, abdomen contact, the time limit, flagged from outside."""
+    from tests import env_pack_ref as R
+    n, steps = 257, 60
+    cfg = O.default_config(n, variant)
+    fused, split = make_env(n, variant), make_env(n, variant)
+    push_state(fused, death_seed_state(cfg, n))
+    rng = np.random.default_rng(17)
+    a0 = pose_actions(cfg, n)
+    seen = dict(d_hi=0, d_lo=0, d_ori=0, d_abd=0, abd_alone=0, timeout_alone=0, outside=0, resets=0)
+    for t in range(steps):
+        a = np.clip(a0 + rng.normal(0, 0.7, (n, 18)), -1, 1).astype(np.float32)
+        a[:8] = 1.0                                        # every joint to its upper limit: these fall over
+        if t in (7, 30):
+            fused.reset_buf[40:44] = 1                      # flagged from outside (the viewer's R key, fly.py:498-500)
+        pre = pull_state(fused)
+        seen["outside"] += int(pre.reset[40:44].sum()) if t in (7, 30) else 0
+        seen["resets"] += int(pre.reset.sum())
+        push_state(split, pre)
+        fused.step(cuda(a))
+        split.set_actions(cuda(a))
+        if not cfg.reset_after_sim:
+            split._lib.fly_reset_masked(split._handle, C.byref(split._bufs), None)
+        split.simulate()
+        if cfg.reset_after_sim:
+            split._lib.fly_reset_masked(split._handle, C.byref(split._bufs), None)
+        split.get_obs()
+        split._lib.fly_pack_reward(split._handle, C.byref(split._bufs), 1, None)
+        f, u = pull_state(fused), pull_state(split)
+        for k in ("root", "dof_pos", "dof_vel", "targets", "contact", "pot", "prev_pot", "obs", "reward", "reset", "progress"):
+            assert np.array_equal(getattr(f, k), getattr(u, k)), (variant, t, k)
+        ref = R.reward_ref(cfg, f.obs, f.targets, f.root, f.contact, f.pot, f.prev_pot, f.progress, np.zeros(n, np.int64))
+        assert np.array_equal(f.reset, ref["reset"]), (variant, t)
+        assert np.all(f.reward[ref["dead"]] == np.float32(cfg.death_cost))
+        for k in ("d_hi", "d_lo", "d_ori", "d_abd"):
+            seen[k] += int(ref[k].sum())
+        seen["abd_alone"] += int((ref["d_abd"] & ~(ref["d_hi"] | ref["d_lo"] | ref["d_ori"])).sum())
+        seen["timeout_alone"] += int((ref["timeout"] & ~ref["dead"]).sum())
+    fused.exit(); split.exit()
+    print(variant, seen)
+    seen.pop("abd_alone")                                  # (reported only: whether a later faller meets no other end first is chaotic)
+    assert all(v > 0 for v in seen.values()), (variant, seen)
+    assert seen["resets"] > seen["outside"] + 20           # and the flagged envs did go through the reset, many times
+
+
 @pytest.mark.parametrize("n", [8192, 8190, 4099, 16384])
 def test_full_size_properties(n):
     """BASELINE size (8192 envs) and ragged tails: determinism, env-permutation equivariance
