@@ -222,6 +222,34 @@ class Fly:
         """[N] int32 view of each env's draw count (None if randomisation was never on)."""
         return None if self._dr_table is None else self._dr_table[:, _lib.DR_PARAMS].view(torch.int32)
 
+    # ---- exact resume (train_state.py, DESIGN.md 3.3f) ------------------------------------------
+    # every tensor FlyBuffers points at except obs and reward, which are rows of the caller's rollout
+    _STATE_TENSORS = ("root_tensor", "dof_states", "actions", "force_tensor", "potentials", "prev_potentials", "reset_buf",
+                      "progress_buf", "episode_return_buf", "episode_length_buf", "finished_return_sum", "finished_length_sum",
+                      "finished_count")
+
+    def training_state(self):
+        """The env's state between two steps, tensors on the CPU: the simulation state, the CURRENT reset / progress flags
+        (`reset_buf` / `progress_buf` may be rows of the caller's per-step flag tensors: their values are what counts), the
+        episode statistics, the step count, and with randomisation the whole table (multipliers and draw counts).  The
+        recorder is not part of it.  A host sync."""
+        from .train_state import pack
+        state = {k: pack(getattr(self, k)) for k in self._STATE_TENSORS}
+        state["render_count"] = int(self.render_count)
+        if self._dr_on:
+            state["dr_table"] = pack(self._dr_table)
+        return state
+
+    def load_training_state(self, state):
+        """training_state() back, in place: the flags go into whatever `reset_buf` / `progress_buf` are now (the env's own
+        tensors in a new process), the table into the one the handle already points at, over the constructor's first draw."""
+        from .train_state import restore, value
+        for k in self._STATE_TENSORS:
+            restore(getattr(self, k), state, "env", k)
+        self.render_count = value(state, "env", "render_count", int)
+        if self._dr_on:
+            restore(self._dr_table, state, "env", "dr_table")
+
     def step(self, actions):
         """fly.py:624-681 in one launch."""
         a = self._check_actions(actions)

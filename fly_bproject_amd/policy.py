@@ -536,6 +536,35 @@ class PackedPolicy:
         """Device int32 [1]: optimizer steps applied so far."""
         return self._step2[self._step_idx:self._step_idx + 1]
 
+    # ---- exact resume (train_state.py, DESIGN.md 3.3f) ------------------------------------------
+    # The master weights and Adam's moments and counter; the derived copies PF / PT / PB / PTB as mlp_adam_step's scatter left
+    # them (stored, not rebuilt: nothing then rests on the torch-side split matching the kernel's bit for bit); the fp16x2 step
+    # verbatim -- the planes, and the whole scale table with the lagged class scales, the weight scales and the rescale
+    # bookkeeping in it.  G, the norm workspace, the saved activations, the tile flags and the sticky words are scratch of an
+    # optimizer step: between updates they hold nothing a later step reads.
+    _STATE_TENSORS = ("P", "exp_avg", "exp_avg_sq", "_step2", "PF", "PT", "PB", "PTB", "PH", "PTH", "h2_scales")
+    _STATE_VALUES = (("_step_idx", int), ("steps_issued", int), ("h2_calibrated", bool), ("h2_overflows", int),
+                     ("h2_calibration_failures", int), ("fuse_fwd_bwd", bool))
+
+    def training_state(self):
+        """Everything of this policy that an interrupted run needs back, tensors on the CPU.  A host sync."""
+        from .train_state import pack
+        state = {k.lstrip("_"): pack(getattr(self, k)) for k in self._STATE_TENSORS}
+        state.update({k.lstrip("_"): kind(getattr(self, k)) for k, kind in self._STATE_VALUES})
+        return state
+
+    def load_training_state(self, state):
+        """training_state() back, in place -- and NOT through refresh(), which would rebuild the planes, rewrite the scale
+        table and clear the calibration.  Call it after everything that does (a gemm selection, broadcast_policy)."""
+        from .train_state import restore, value
+        for k in self._STATE_TENSORS:
+            restore(getattr(self, k), state, "policy", k.lstrip("_"))
+        for k, kind in self._STATE_VALUES:
+            setattr(self, k, value(state, "policy", k.lstrip("_"), kind))
+        self.h2_overflow.zero_()
+        self.h2_suspended = False
+        self.version += 1                                   # cached network outputs are of other weights
+
     def adam_step(self, grad_scale=1.0, norm_ready=False, self_norm=False, grad_invalid=None):
         """clip_grad_norm_ + Adam on the packed parameters.  norm_ready: mlp_grad_w has already left the norm
         partials and advanced the step (single rank).  self_norm: ONE launch that also sums the gradient

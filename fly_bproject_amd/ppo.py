@@ -28,7 +28,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, train_state
 from .fly import Fly
 from .params import NUM_DOF
 
@@ -147,6 +147,20 @@ class PPO:
         self.noise_rho = float(getattr(args, "noise_rho", 0.5))
         if not 0.0 < self.noise_rho < 1.0:
             raise ValueError("noise_rho must be in (0, 1) (got %r)" % (self.noise_rho,))
+        # opt-in (`resume`, trainer.py --resume_path): the run continues the one that wrote `resume_path` with `save_state`, bit
+        # for bit.  The state file is read and its meta held against these args HERE, before the env exists: a
+        # state of another shape or option must not leave an env behind either.  load_training_state() applies it.
+        self._resume_state = None
+        if getattr(args, "resume", False):
+            if getattr(args, "load", False):
+                raise ValueError("resume and load exclude each other: resume_path names the weights file too")
+            if getattr(args, "testing", False):
+                raise ValueError("resume continues a training run: it has no meaning with testing")
+            if getattr(args, "resume_path", None) is None:
+                raise ValueError("resume needs resume_path: a weights file written by a save_state run")
+            self._resume_state = train_state.read_state_file(
+                self.training_state_path(args.resume_path, int(getattr(args, "rank", 0) or 0)))
+            train_state.check_meta(self._resume_state.get("meta"), args)
         self.env = env if env is not None else Fly(args)           # ppo.py:110
         self.num_acts = self.env.num_act
         self.num_obs = self.env.num_obs
@@ -219,15 +233,15 @@ class PPO:
             self._ended_prev = self.env.reset_buf.clone()
         # opt-in (`minibatch="shuffled"`): every epoch draws its 15 minibatches from a fresh keyed permutation of ALL T * N rows
         # of the rollout, gathered into one staging set in front of the unchanged optimizer-step kernels.  NOT
-        # the reference's contiguous-in-time slices (Q3).  Nothing of it goes into a checkpoint: a resumed run counts its
-        # updates, and with them its epoch keys, from 0 again.
+        # the reference's contiguous-in-time slices (Q3).  Nothing of it goes into the weights file; `--save_state` carries it
+        # (the count of updates, and with it the epoch keys).
         self._mb_stage = self._mb_index = None
         if self.minibatch == "shuffled":
             self._setup_minibatch()
         # opt-in (`action_noise="ar1"`): the rollout's noise is an AR(1) process along time with unit stationary variance, made
         # by one filter launch over `_eps_all` right behind the white draw.  NOT the reference's sampling.  The
         # carry [N, 18] is the process' last row: drawn once before the first rollout (`_draw_noise`), then handed from rollout
-        # to rollout by the launch.  Nothing of it goes into a checkpoint or to another rank.
+        # to rollout by the launch.  Nothing of it goes into the weights file (`--save_state` carries it) or to another rank.
         self._noise_carry, self._noise_carry_drawn = None, False
         if self.action_noise == "ar1":
             self._noise_carry = torch.zeros((n, self.num_acts), device=dev)
@@ -251,6 +265,7 @@ class PPO:
         self.log_throughput = bool(getattr(args, "log_throughput", False))
         self._rate_mark = None                                      # (perf_counter, run_step) of the previous score line
         self._pending_step = None                                   # deferred check of the device step counter (_update_hip)
+        self._in_run_tail = False                                   # True inside run()'s periodic save (save_training_state)
         self.env.bind_obs(self._obs_ring[0])                        # first policy input: zeros (Q8)
 
         self.score = 0
@@ -259,6 +274,12 @@ class PPO:
 
         self.net = Net(self.env.num_obs, self.env.num_act).to(dev)
         loaded_rms, loaded_value_rms = {}, {}
+        if self._resume_state is not None:                          # the weights file, as `load` below takes it
+            print("resuming from: ", str(self.args.resume_path))
+            sd = torch.load(self.args.resume_path, map_location=dev, weights_only=True)
+            loaded_rms = split_obs_rms(sd, self.normalize_obs)
+            loaded_value_rms = split_value_rms(sd, self.normalize_value)
+            self.net.load_state_dict(sd)
         if getattr(self.args, "load", False):                       # ppo.py:147-149
             print("loaded from: ", str(self.args.load_path))
             sd = torch.load(self.args.load_path, map_location=dev, weights_only=True)
@@ -458,7 +479,7 @@ class PPO:
         """The one staging minibatch (obs | action | log-prob | target | advantage rows, 376 B per row: 15.4 MB at the default
         shape; stream order makes one set enough), this rank's seed (`minibatch_seed`, default `seed`, + rank * 0x9E3779B9
         wrapping, as domain randomisation) and the count of update() calls the epoch keys are derived from.  Nothing of it goes
-        into a checkpoint: a resumed run counts its updates from 0 again."""
+        into the weights file; `--save_state` carries it."""
         dev, rows = self.device, self.mini_chunk_size * int(self.args.num_envs)
         seed = getattr(self.args, "minibatch_seed", None)
         if seed is None:
@@ -1158,7 +1179,11 @@ class PPO:
             self.env.bind_obs(self._obs_ring[0])
             if getattr(self.args, "save", False) and self.optim_step % self.args.save_freq == 0 and self.optim_step != 0:
                 self._emit("saving...")
-                self.save(str(self.optim_step))
+                self._in_run_tail = True                            # this call's `run_step += 1` is still to come (save_training_state)
+                try:
+                    self.save(str(self.optim_step))
+                finally:
+                    self._in_run_tail = False
                 self._emit("saved!")
         else:
             self.mini_batch_number += 1
@@ -1174,20 +1199,142 @@ class PPO:
         return end
 
     def save(self, endofname=""):
-        """ppo.py:266-273: state_dict only, reference key names."""
+        """ppo.py:266-273: state_dict only, reference key names, written by rank 0.  With `save_state` EVERY rank also writes
+        its training state beside it (save_training_state) -- at a rollout boundary; inside a rollout only the weights."""
         if not getattr(self.args, "save", False):
             return
         self._check_step_counter()
-        if int(getattr(self.args, "rank", 0)) != 0:
-            return
+        rank = int(getattr(self.args, "rank", 0))
         path = self.args.save_path + endofname + ".pth"
-        # parameters are views of the packed buffer: save compact, contiguous copies
-        sd = {k: v.detach().clone().contiguous() for k, v in self.net.state_dict().items()}
-        if self.normalize_obs:                                      # only then: otherwise the file is the reference's
-            sd["obs_rms.mean"], sd["obs_rms.var"], sd["obs_rms.count"] = self.obs_mean, self.obs_var, self.obs_count
+        if rank == 0:
+            # parameters are views of the packed buffer: save compact, contiguous copies
+            sd = {k: v.detach().clone().contiguous() for k, v in self.net.state_dict().items()}
+            if self.normalize_obs:                                  # only then: otherwise the file is the reference's
+                sd["obs_rms.mean"], sd["obs_rms.var"], sd["obs_rms.count"] = self.obs_mean, self.obs_var, self.obs_count
+            if self.normalize_value:
+                sd["value_rms.mean"], sd["value_rms.var"], sd["value_rms.count"] = self.value_mean, self.value_var, self.value_count
+            torch.save(sd, path)
+        if not getattr(self.args, "save_state", False):
+            return
+        if self.mini_batch_number != 0:
+            # with one launch per rollout the device is a whole rollout ahead of the host: there is no state "at step t"
+            if rank == 0:
+                self._emit("save_state: step %d of %d of a rollout: %s holds the weights only, no training state; the last periodic "
+                           "save is the one to resume from" % (self.mini_batch_number, self.rollout_size, path))
+                self.flush_log()
+            return
+        self.save_training_state(self.training_state_path(path, rank))
+
+    # ------------------------------------------------------------------------------------------
+    # exact resume (opt-in: `save_state`, `resume`; DESIGN.md 3.3f)
+    training_state_path = staticmethod(train_state.training_state_path)
+
+    def _training_state_meta(self):
+        """The meta block of THIS run: the args' (train_state.expected_meta), with what the live objects report in place of
+        what the args predict."""
+        meta = train_state.expected_meta(self.args)
+        meta.update(rollout_size=int(self.rollout_size), gemm=self.policy.gemm, step_gemm=self.policy.step_gemm,
+                    persistent_rollout=bool(self.persistent_rollout), dp_mode=self.dp_mode)
+        return meta
+
+    def save_training_state(self, path):
+        """Everything between the kernels and the public interface that the next rollout and update read, into `path`
+        (train_state.py has the format): with the weights file beside it, a new process continues this run bit for bit.
+        Only at a ROLLOUT BOUNDARY (mini_batch_number == 0: after the update, after ring[0] <- ring[T]); ValueError inside a
+        rollout.  Host-synchronising; the log queue is drained first.  Not restored, so not stored: the recorder, the
+        peer-to-peer windows (prepare() reopens them), and the torch backend's optimizer (ValueError)."""
+        if self.mini_batch_number != 0:
+            raise ValueError("save_training_state: step %d of %d of a rollout; a training state exists only at a rollout boundary"
+                             % (self.mini_batch_number, self.rollout_size))
+        if self.update_backend != "hip":
+            raise ValueError("save_training_state: update_backend=%r keeps its optimizer state in torch.optim.Adam, which is not "
+                             "part of a training state" % (self.update_backend,))
+        if getattr(self, "_book_terms", None) is not None:
+            self._flush_bookkeeping()
+        self._check_step_counter()
+        self.flush_log()
+        run_step = self.run_step
+        if self._in_run_tail:
+            # run()'s periodic save: the call still has its score check and `run_step += 1` ahead.  No score line is due there
+            # (rollout_size is a multiple of 16, so run_step is odd), so the state is the one after the call.
+            assert run_step % self.num_eval_freq != 0
+            run_step += 1
+        pack = train_state.pack
+        agent = {"run_step": int(run_step), "optim_step": int(self.optim_step), "action_var": pack(self._action_var),
+                 "score_acc": pack(self._score_acc), "generator": pack(self._gen.get_state()), "obs_row0": pack(self._obs_ring[0])}
+        if self.action_noise == "ar1":
+            agent["noise_carry"], agent["noise_carry_drawn"] = pack(self._noise_carry), bool(self._noise_carry_drawn)
+        if self.minibatch == "shuffled":
+            agent["mb_update"] = int(self._mb_update)
+        if self.gae == "episodic":
+            agent["ended_prev"] = pack(self._ended_prev)
+        if self.normalize_obs:
+            agent["obs_stats"], agent["obs_table"] = pack(self._obs_stats), pack(self._obs_table)
         if self.normalize_value:
-            sd["value_rms.mean"], sd["value_rms.var"], sd["value_rms.count"] = self.value_mean, self.value_var, self.value_count
-        torch.save(sd, path)
+            for k in ("value_stats", "value_table", "value_stats_next", "value_table_next"):
+                agent[k] = pack(getattr(self, "_" + k))
+        state = {"format": train_state.FORMAT, "meta": self._training_state_meta(), "policy": self.policy.training_state(),
+                 "agent": agent, "env": self.env.training_state()}
+        tmp = path + ".tmp"
+        torch.save(state, tmp)
+        os.replace(tmp, path)                                       # a run cut off in the middle of a save leaves the previous file whole
+
+    def load_training_state(self, path=None):
+        """save_training_state() back into this agent, in place; `path` defaults to the state file beside `args.resume_path`
+        (already read and checked by the constructor).  Call it LAST: after a gemm selection and after broadcast_policy, which
+        rebuild the planes and clear the fp16x2 calibration.  The meta is held against the live objects once more (a gemm set
+        after construction), and the float64 statistics the weights file carried must be the state file's."""
+        if path is None and self._resume_state is not None:
+            state = self._resume_state
+        else:
+            if path is None:
+                if getattr(self.args, "resume_path", None) is None:
+                    raise ValueError("load_training_state: no path given and no args.resume_path")
+                path = self.training_state_path(self.args.resume_path, int(getattr(self.args, "rank", 0) or 0))
+            state = train_state.read_state_file(path)
+        self._resume_state = None
+        if self.mini_batch_number != 0:
+            raise ValueError("load_training_state: step %d of %d of a rollout; a training state goes in only at a rollout boundary"
+                             % (self.mini_batch_number, self.rollout_size))
+        if self.update_backend != "hip":
+            raise ValueError("load_training_state: update_backend=%r is not part of a training state" % (self.update_backend,))
+        train_state.compare_meta(state.get("meta"), self._training_state_meta())
+        agent = train_state.block(state, "agent")
+        restore, value = train_state.restore, train_state.value
+        for mine, key, on in ((getattr(self, "_obs_stats", None), "obs_stats", self.normalize_obs),
+                              (getattr(self, "_value_stats", None), "value_stats", self.normalize_value)):
+            if on and torch.is_tensor(agent.get(key)) and not torch.equal(mine.cpu(), agent[key]):
+                raise ValueError("training state: %s of the weights file %s and of the state file disagree; they are not of the same "
+                                 "save" % (key, mine.cpu().tolist()[:3]))
+        self._check_step_counter()
+        self.flush_log()
+        self.policy.load_training_state(train_state.block(state, "policy"))
+        self.env.load_training_state(train_state.block(state, "env"))
+        self.run_step, self.optim_step = value(agent, "agent", "run_step", int), value(agent, "agent", "optim_step", int)
+        if getattr(self, "_book_terms", None) is not None:
+            self._flush_bookkeeping()                               # (an agent that has run: nothing pending on the old variance)
+        restore(self._action_var, agent, "agent", "action_var")
+        restore(self._score_acc, agent, "agent", "score_acc")
+        gen = self._gen.get_state()
+        restore(gen, agent, "agent", "generator")
+        self._gen.set_state(gen)
+        restore(self._obs_ring[0], agent, "agent", "obs_row0")
+        self._v_have = 0
+        if self.action_noise == "ar1":
+            restore(self._noise_carry, agent, "agent", "noise_carry")
+            self._noise_carry_drawn = value(agent, "agent", "noise_carry_drawn", bool)
+        if self.minibatch == "shuffled":
+            self._mb_update = value(agent, "agent", "mb_update", int)
+        if self.gae == "episodic":
+            restore(self._ended_prev, agent, "agent", "ended_prev")
+        if self.normalize_obs:
+            restore(self._obs_stats, agent, "agent", "obs_stats")
+            restore(self._obs_table, agent, "agent", "obs_table")
+        if self.normalize_value:
+            for k in ("value_stats", "value_table", "value_stats_next", "value_table_next"):
+                restore(getattr(self, "_" + k), agent, "agent", k)
+        self._rate_mark = None
+        torch.cuda.synchronize(self.device)
 
     def generate_video(self):
         return self.env.generate_video()

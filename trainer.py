@@ -17,14 +17,25 @@ the reference's estimator with its quirks).
 `--minibatch shuffled` (every epoch draws its 15 minibatches from a fresh permutation of ALL rows of the rollout, DESIGN.md
 3.3e; the default `reference` is the reference's 15 contiguous-in-time slices, the same in every epoch, the 16th chunk never
 visited) with `--minibatch_seed` (default `--seed`; rank r adds r * 0x9E3779B9).  The permutation is a pure function of the seed,
-the count of updates and the epoch: nothing of it goes into the checkpoint, and a resumed run counts its updates from 0 again.
+the count of updates and the epoch: nothing of it goes into the weights file; `--save_state` carries the count.
 `--action_noise ar1` (temporally correlated exploration noise, DESIGN.md 3.2b: the rollout's noise is an AR(1) process along
 time with unit stationary variance and lag-1 correlation `--noise_rho`, default 0.5; the default `white` is the reference's
 independent draw at every step).  Each step's noise is still N(0, 1), so the stored log-probs stay the densities of the actions.
-The process runs on from rollout to rollout and is not restarted at episode ends; nothing of it goes into the checkpoint.
+The process runs on from rollout to rollout and is not restarted at episode ends; nothing of it goes into the weights file;
+`--save_state` carries it.
 `--randomize` (per-env physics domain randomisation, off by default): each env runs on its own multipliers of kp, kd, effort,
 mass (and inertia), mu and gravity, drawn from `--dr_<name> LO HI` at every reset of that env with seed `--dr_seed` (default
-`--seed`; rank r adds r * 0x9E3779B9).  A property of the env: nothing of it goes into the checkpoint.
+`--seed`; rank r adds r * 0x9E3779B9).  A property of the env: nothing of it goes into the weights file; `--save_state` carries it.
+`--save_state` (with `--save_path`) and `--resume_path FILE` (exact resume).  The weights file stays the
+reference's; with `--save_state` every save made at a rollout boundary (all periodic ones) also writes, on EVERY rank,
+`<save_path><suffix>.state.r<rank>.pth`: Adam's moments and counter, the fp16x2 scales and planes, the step counts and the
+action variance, the generator, the env's state and episode statistics, the normalisation statistics, the noise carry, the
+minibatch update count and the randomisation table.  `--resume_path FILE` names a weights file of such a run: the weights load
+as `--load_path` loads them, each rank's state comes from the file beside it, and the run goes on bit for bit as if it had
+never stopped -- under exactly the options it was saved with (any difference is an error naming the option; `--load_path`
+takes the weights alone).  A save inside a rollout (the end-of-run save after a `--max_steps` that is no multiple of the
+rollout) writes the weights only and says so.  Not restored: the recorder's frame numbering; `--resume_path` excludes
+`--load_path` and `--testing`.
 Recording (`--record True` or `--record_dir_name DIR`): rank 0 renders env 0 on the GPU every
 `--time_steps_per_recorded_frame` env steps to DIR/frame_%06d.png (fly_bproject_amd/record.py) and, when ffmpeg is on
 PATH, assembles DIR.mp4 at the end.  Unlike the reference, which records only with its viewer open, recording does not
@@ -110,6 +121,12 @@ def parse_args(argv=None):
         parser.add_argument('--dr_' + name, type=float, nargs=2, default=list(DR_DEFAULT_RANGES[name]), metavar=('LO', 'HI'),
                             help='range of the %s multiplier (with --randomize; mass scales the inertia too)' % name)
     parser.add_argument('--dr_seed', type=int, default=None, help='seed of the randomisation draws (default: --seed)')
+    parser.add_argument('--save_state', action='store_true',
+                        help='with --save_path: every save at a rollout boundary also writes <save_path><suffix>.state.r<rank>.pth, '
+                             'the full training state of each rank, for --resume_path (off by default: the weights file alone)')
+    parser.add_argument('--resume_path', type=str, default=None,
+                        help='a weights file written by a --save_state run: continue that run bit for bit from it and the state '
+                             'files beside it, under the same options (excludes --load_path and --testing)')
     args = parser.parse_args(argv)
     if args.save_path is not None:          # trainer.py:27-34
         args.save = True
@@ -117,6 +134,13 @@ def parse_args(argv=None):
         args.load = True
     if args.record_dir_name is not None:
         args.record = True
+    args.resume = args.resume_path is not None
+    if args.resume and args.load:
+        parser.error("--resume_path and --load_path exclude each other (--resume_path names the weights file too)")
+    if args.resume and args.testing:
+        parser.error("--resume_path continues a training run: it has no meaning with --testing")
+    if args.save_state and args.save_path is None:
+        parser.error("--save_state needs --save_path")
     return args
 
 
@@ -137,6 +161,8 @@ def main(argv=None):
     if args.gemm:
         policy.policy.gemm = args.gemm
     broadcast_policy(policy)
+    if args.resume:
+        policy.load_training_state()        # last: the two calls above rebuild planes and clear the fp16x2 calibration
     end = False                             # trainer.py:41-44
     while not end:
         end = policy.run()
