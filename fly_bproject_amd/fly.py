@@ -18,15 +18,8 @@ import math
 import torch
 
 from . import _lib
+from .options import DR_DEFAULT_RANGES, DR_NAMES, dr_args, resolve_env  # noqa: F401  (the randomisation's names live there)
 from .params import NUM_CONTACT, NUM_DOF, NUM_OBS, ROOT_DIM, default_params
-
-# per-env physics domain randomisation (include/flyhip.h, fly_set_randomization): multipliers of these FlyConfig values, in
-# this order; `mass` scales the inertia too
-DR_NAMES = ("kp", "kd", "effort", "mass", "mu", "gravity")
-# trainer.py's starting ranges (--dr_*): not tuned
-DR_DEFAULT_RANGES = {"kp": (0.8, 1.2), "kd": (0.8, 1.2), "effort": (1.0, 1.0), "mass": (0.8, 1.2), "mu": (0.5, 1.5),
-                     "gravity": (1.0, 1.0)}
-DR_RANK_STRIDE = 0x9E3779B9         # rank r of a data-parallel run draws with seed + r * this (mod 2^32)
 
 
 def dr_bounds(ranges):
@@ -52,29 +45,14 @@ def dr_bounds(ranges):
     return lo, hi
 
 
-def dr_args(args):
-    """(ranges, seed) of `args.randomize`: the --dr_* ranges (defaults DR_DEFAULT_RANGES), and --dr_seed (default --seed)
-    offset by the rank, so that the ranks of a data-parallel run draw different constants."""
-    ranges = {}
-    for name in DR_NAMES:
-        v = getattr(args, "dr_" + name, None)
-        ranges[name] = tuple(v) if v is not None else DR_DEFAULT_RANGES[name]
-    seed = getattr(args, "dr_seed", None)
-    if seed is None:
-        seed = getattr(args, "seed", 0) or 0
-    rank = int(getattr(args, "rank", 0) or 0)
-    return ranges, (int(seed) + DR_RANK_STRIDE * rank) % (1 << 32)
-
-
 class Fly:
     def __init__(self, args, params=None):
         self.args = args
+        opts = resolve_env(args)
         self.end = False                                  # fly.py:15
         self.up_axis_idx = 2
-        n = int(args.num_envs)
-        variant = getattr(args, "variant", "bigGrav")
-        reward = getattr(args, "reward", "standing")
-        self.params = params if params is not None else default_params(n, variant, reward)
+        n = opts.num_envs
+        self.params = params if params is not None else default_params(n, opts.variant, opts.reward)
         if self.params.num_envs != n:
             raise ValueError("params.num_envs (%d) != args.num_envs (%d)" % (self.params.num_envs, n))
         self.dt = float(self.params.dt)                   # fly.py:16
@@ -139,15 +117,13 @@ class Fly:
         self._dr_on = False
         # bumped whenever the kernels a launch selects change (randomisation on / off): captured graphs hold the old ones
         self.launch_form = 0
-        if getattr(args, "randomize", False):
-            ranges, seed = dr_args(args)
-            self.set_randomization(ranges, seed)
+        if opts.randomize:
+            self.set_randomization(dict(zip(DR_NAMES, opts.dr_ranges)), opts.dr_seed)
         # recording (fly.py:592-610): env 0, rank 0 only (record.py)
         self.recorder = None
-        if getattr(args, "record", False) and int(getattr(args, "rank", 0) or 0) == 0:
+        if opts.record:
             from .record import Recorder
-            self.recorder = Recorder(self, getattr(args, "record_dir_name", None) or "recording",
-                                     getattr(args, "time_steps_per_recorded_frame", 2))
+            self.recorder = Recorder(self, opts.record_dir_name, opts.time_steps_per_recorded_frame)
 
     # ------------------------------------------------------------------------------------------
     def _refresh_pointers(self):

@@ -10,7 +10,7 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, options
 
 IN, IN_PAD, H1, H2, H3, OUT, NACT = 73, 80, 256, 128, 128, 32, 18
 OFF_W1 = 0
@@ -154,19 +154,19 @@ class PackedPolicy:
         self.PT = torch.zeros(FRAG_T, dtype=torch.float32, device=self.device)    # W^T operands, fragment order
         # GEMM arithmetic of the MFMA kernels: "bf16x3" (default) = three-term bf16 split of both fp32 operands on
         # v_mfma_f32_32x32x16_bf16, fp32 accumulate (held to the reference's golden vectors at the fp32 tolerances and to fp64:
-        # tests/test_ppo_gpu.py, tests/test_mlp_train_gpu.py, csrc/mlp_layout.h); "f32" = v_mfma_f32_32x32x2_f32 (FLY_GEMM=f32)
-        env_gemm = os.environ.get("FLY_GEMM")               # names EVERY GEMM when given ("f16x2": bf16x3 + the fp16x2 optimizer step)
-        self._gemm = "bf16x3" if env_gemm in (None, "f16x2") else env_gemm
+        # tests/test_ppo_gpu.py, tests/test_mlp_train_gpu.py, csrc/mlp_layout.h); "f32" = v_mfma_f32_32x32x2_f32.  What the
+        # environment selects for a policy of its own (options.resolve_gemm has the rule and names the variables)
+        self._gemm, step_gemm = options.resolve_gemm(None, os.environ)
         self.gemm_infer = os.environ.get("FLY_GEMM_INFER", self._gemm)
         assert self._gemm in ("f32", "bf16x3") and self.gemm_infer in ("f32", "bf16x3")
         self.PB = torch.zeros(PB_HALVES, dtype=torch.int16, device=self.device)
         self.PTB = torch.zeros(PTB_HALVES, dtype=torch.int16, device=self.device)
         # Arithmetic of the fused optimizer-step gradient (only): "bf16x3" (mlp_fused_grad) or "f16x2" (mlp_fused_grad_h2: two fp16 terms
         # per operand, three products per k block, per-class power-of-two scales; csrc/mlp_fused_h2.inc).  The rollout's policy, the
-        # critic pass and every fallback stay on `gemm`.  FLY_STEP_GEMM / --step_gemm / policy.step_gemm = ...
-        # DEFAULT (round 5): f16x2, with bf16x3 as the A/B and as the fallback of a refused step; `policy.gemm = "bf16x3"` (or
-        # FLY_GEMM=bf16x3) names every GEMM, the step included.
-        self._step_gemm = os.environ.get("FLY_STEP_GEMM", "f16x2" if env_gemm in (None, "f16x2") else "bf16x3")
+        # critic pass and every fallback stay on `gemm`.  policy.step_gemm = ...
+        # DEFAULT (round 5): f16x2, with bf16x3 as the A/B and as the fallback of a refused step; `policy.gemm = "bf16x3"`
+        # names every GEMM, the step included.  (Under f32 the step is f32 and this selection is not looked at: see step_gemm.)
+        self._step_gemm = step_gemm if self._gemm == "bf16x3" else "bf16x3"
         assert self._step_gemm in ("bf16x3", "f16x2")
         self.PH = torch.zeros(PH_HALVES, dtype=torch.int16, device=self.device)
         self.PTH = torch.zeros(PTH_HALVES, dtype=torch.int16, device=self.device)

@@ -28,9 +28,14 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib, train_state
+from . import _lib, options, train_state
 from .fly import Fly
 from .params import NUM_DOF
+
+
+def p(x):
+    """The device address of a tensor, as the C ABI takes it."""
+    return C.c_void_p(x.data_ptr())
 
 
 class Net(nn.Module):
@@ -67,34 +72,32 @@ def diag_gauss_logprob(mu, action, var):
 
 
 OBS_RMS_KEYS = ("obs_rms.mean", "obs_rms.var", "obs_rms.count")
-
-
-def split_obs_rms(state_dict, normalize_obs):
-    """Remove the observation statistics (obs_rms.*) from a loaded state dict, in place, and return them: the rest then loads
-    strictly into Net (a reference checkpoint has none).  Statistics without `normalize_obs` are an error: the network was
-    trained on normalised inputs."""
-    rms = {k: state_dict.pop(k) for k in list(state_dict) if k.startswith("obs_rms.")}
-    if rms and not normalize_obs:
-        raise ValueError("this checkpoint was trained with observation normalisation (it holds %s): run with --normalize_obs"
-                         % ", ".join(sorted(rms)))
-    if rms and sorted(rms) != sorted(OBS_RMS_KEYS):
-        raise ValueError("incomplete observation statistics in the checkpoint: %s (want %s)" % (sorted(rms), list(OBS_RMS_KEYS)))
-    return rms
-
-
 VALUE_RMS_KEYS = ("value_rms.mean", "value_rms.var", "value_rms.count")
 
 
-def split_value_rms(state_dict, normalize_value):
-    """split_obs_rms for the value statistics (value_rms.*): removed from the state dict, in place, and returned.  Statistics
-    without `normalize_value` are an error: the critic was trained on normalised targets, its outputs are not in reward units."""
-    rms = {k: state_dict.pop(k) for k in list(state_dict) if k.startswith("value_rms.")}
-    if rms and not normalize_value:
-        raise ValueError("this checkpoint was trained with value normalisation (it holds %s): run with --normalize_value"
-                         % ", ".join(sorted(rms)))
-    if rms and sorted(rms) != sorted(VALUE_RMS_KEYS):
-        raise ValueError("incomplete value statistics in the checkpoint: %s (want %s)" % (sorted(rms), list(VALUE_RMS_KEYS)))
+def _split_rms(state_dict, keys, on, what, flag):
+    """Remove the `what` statistics (`keys`, one prefix) from a loaded state dict, in place, and return them: the rest then
+    loads strictly into Net (a reference checkpoint has none).  Statistics while the option is not `on` are an error."""
+    prefix = keys[0].split(".")[0] + "."
+    rms = {k: state_dict.pop(k) for k in list(state_dict) if k.startswith(prefix)}
+    if rms and not on:
+        raise ValueError("this checkpoint was trained with %s normalisation (it holds %s): run with --%s"
+                         % (what, ", ".join(sorted(rms)), flag))
+    if rms and sorted(rms) != sorted(keys):
+        raise ValueError("incomplete %s statistics in the checkpoint: %s (want %s)" % (what, sorted(rms), list(keys)))
     return rms
+
+
+def split_obs_rms(state_dict, normalize_obs):
+    """The observation statistics (obs_rms.*) out of a loaded state dict.  Without `normalize_obs` they are an error: the
+    network was trained on normalised inputs."""
+    return _split_rms(state_dict, OBS_RMS_KEYS, normalize_obs, "observation", "normalize_obs")
+
+
+def split_value_rms(state_dict, normalize_value):
+    """The value statistics (value_rms.*) out of a loaded state dict.  Without `normalize_value` they are an error: the critic
+    was trained on normalised targets, its outputs are not in reward units."""
+    return _split_rms(state_dict, VALUE_RMS_KEYS, normalize_value, "value", "normalize_value")
 
 
 def value_norm_table(stats):
@@ -135,31 +138,19 @@ def combine_adv_stats(ranks, count):
 class PPO:
     def __init__(self, args, env=None):
         self.args = args
-        self.gae = getattr(args, "gae", "reference")                # read first: a bad value must not leave an env behind
-        if self.gae not in ("reference", "episodic"):
-            raise ValueError("gae must be reference or episodic (got %r)" % (self.gae,))
-        self.minibatch = getattr(args, "minibatch", "reference")
-        if self.minibatch not in ("reference", "shuffled"):
-            raise ValueError("minibatch must be reference or shuffled (got %r)" % (self.minibatch,))
-        self.action_noise = getattr(args, "action_noise", "white")
-        if self.action_noise not in ("white", "ar1"):
-            raise ValueError("action_noise must be white or ar1 (got %r)" % (self.action_noise,))
-        self.noise_rho = float(getattr(args, "noise_rho", 0.5))
-        if not 0.0 < self.noise_rho < 1.0:
-            raise ValueError("noise_rho must be in (0, 1) (got %r)" % (self.noise_rho,))
+        self._book_terms = None                                     # nothing to flush until _prepare_step_args
+        # every option, resolved and validated once and first (options.py): a bad value must not leave an env behind.  Only what
+        # callers flip on a live agent is read from `args` later, when it is used: testing, save, save_path, save_freq,
+        # save_state, load_path.
+        opts = self.options = options.resolve(args, os.environ)
+        self.gae, self.minibatch = opts.gae, opts.minibatch
+        self.action_noise, self.noise_rho = opts.action_noise, opts.noise_rho
         # opt-in (`resume`, trainer.py --resume_path): the run continues the one that wrote `resume_path` with `save_state`, bit
         # for bit.  The state file is read and its meta held against these args HERE, before the env exists: a
         # state of another shape or option must not leave an env behind either.  load_training_state() applies it.
         self._resume_state = None
-        if getattr(args, "resume", False):
-            if getattr(args, "load", False):
-                raise ValueError("resume and load exclude each other: resume_path names the weights file too")
-            if getattr(args, "testing", False):
-                raise ValueError("resume continues a training run: it has no meaning with testing")
-            if getattr(args, "resume_path", None) is None:
-                raise ValueError("resume needs resume_path: a weights file written by a save_state run")
-            self._resume_state = train_state.read_state_file(
-                self.training_state_path(args.resume_path, int(getattr(args, "rank", 0) or 0)))
+        if opts.resume:
+            self._resume_state = train_state.read_state_file(self.training_state_path(opts.resume_path, opts.rank))
             train_state.check_meta(self._resume_state.get("meta"), args)
         self.env = env if env is not None else Fly(args)           # ppo.py:110
         self.num_acts = self.env.num_act
@@ -169,14 +160,12 @@ class PPO:
         self.gamma = 0.99
         self.lmbda = 0.95
         self.clip = 0.2
-        self.mini_batch_size = 40960
-        self.chuck_number = 16
-        n = int(args.num_envs)
-        self.mini_chunk_size = self.mini_batch_size // n            # ppo.py:120 (Q9: 0 for N > 40960)
-        if self.mini_chunk_size < 1:
-            raise ValueError("num_envs=%d gives mini_chunk_size 0 (ppo.py:120); use num_envs <= 40960" % n)
+        self.mini_batch_size = options.MINI_BATCH_SIZE
+        self.chuck_number = options.CHUNK_NUMBER
+        n = opts.num_envs
+        self.mini_chunk_size = opts.mini_chunk_size                 # ppo.py:120 (Q9: 0 for N > 40960, refused by the resolver)
         print("mini_chunk_size: ", self.mini_chunk_size)
-        self.rollout_size = self.mini_chunk_size * self.chuck_number
+        self.rollout_size = opts.rollout_size
         print("rollout_size: ", self.rollout_size)
         self.num_eval_freq = 100
         self.mini_batch_number = 0
@@ -191,7 +180,7 @@ class PPO:
         # critic pass of ppo.py:158-159), so make_data only has to evaluate the last next_obs
         self._v_ring = torch.zeros((T + 1, n, 1), device=dev)
         self._v_have, self._v_version = 0, -1
-        self.reuse_rollout_values = bool(getattr(args, "reuse_rollout_values", True))
+        self.reuse_rollout_values = opts.reuse_rollout_values
         self.all_acts = torch.zeros((T, n, self.num_acts), device=dev)
         self.all_reward = torch.zeros((T, n, 1), device=dev)
         self._all_done = None                                        # see the all_done property (Q1)
@@ -200,32 +189,26 @@ class PPO:
         self._target = torch.zeros((T, n, 1), device=dev)
         self._eps_all = torch.zeros((T, n, self.num_acts), device=dev)   # one normal_() per rollout
         self._mu = torch.zeros((n, self.num_acts), device=dev)
-        self.normalize_advantage = bool(getattr(args, "normalize_advantage", False))
+        self.normalize_advantage = opts.normalize_advantage
         self._adv_stats = torch.zeros(514, device=dev)
         # opt-in (`normalize_obs`, rl_games' normalize_input): the policy sees clamp((obs - mean) * rsqrt(var + 1e-5), +-obs_clip)
         # under running statistics of the observations.  The ring keeps the raw rows; see _setup_obs_norm.
-        self.normalize_obs = bool(getattr(args, "normalize_obs", False))
-        self.obs_clip = float(getattr(args, "obs_clip", 5.0))
-        if self.normalize_obs and not self.obs_clip > 0.0:
-            raise ValueError("obs_clip must be > 0 (got %r)" % self.obs_clip)
+        self.normalize_obs, self.obs_clip = opts.normalize_obs, opts.obs_clip
         # opt-in (`normalize_value`, rl_games' normalize_value): the critic regresses on TD targets kept at zero mean / unit
         # variance by running statistics, and make_data maps its outputs back to reward units
-        self.normalize_value = bool(getattr(args, "normalize_value", False))
+        self.normalize_value = opts.normalize_value
         # opt-in (`gae="episodic"`): per-step end flags, a recurrence that stops at episode ends, a bootstrap through time-outs
         # and no training signal from the step that performs a reset.  NOT the reference's estimator (Q1/Q2).
-        # (self.gae, validated above)
-        self.use_graph = bool(getattr(args, "graph", False))
+        # (self.gae, above)
+        self.use_graph = opts.graph
         # one launch per ROLLOUT (ppo_rollout_all): each workgroup loops over the T steps of its own 32 envs.  The device then
         # runs ahead of the host's step count inside a rollout, but everything `run()` reads per step is a ROW the launch wrote
         # for that step: observation / reward / action / log-prob rows as always, and `env.reset_buf` / `env.progress_buf`
         # (fly.py:175-177) are re-pointed at row t of per-step [T, N] tensors -- so it is the default whenever one launch stays
         # short (T <= 4096 steps; the reference's 16-env shape, T = 40 960, steps launch by launch).  `persistent_rollout=False`
-        # (or FLY_PERSISTENT_ROLLOUT=0) keeps one launch per step; the env's STATE tensors (root_tensor, dof_states, ...) show the
-        # rollout's end while the host is still counting through it.
-        want = getattr(args, "persistent_rollout", None)
-        if want is None:
-            want = os.environ.get("FLY_PERSISTENT_ROLLOUT", "1") != "0"
-        self.persistent_rollout = bool(want) and T <= 4096 and not bool(getattr(args, "graph", False))
+        # (or its environment variable at 0, options.py) keeps one launch per step; the env's STATE tensors (root_tensor,
+        # dof_states, ...) show the rollout's end while the host is still counting through it.
+        self.persistent_rollout = opts.persistent_rollout
         self._reset_rows = self._progress_rows = self._ended_prev = None
         if self.gae == "episodic":
             # the end flags the env carries into the first rollout: its initial reset_buf (every env resets in its first step)
@@ -255,14 +238,11 @@ class PPO:
         # queue: a score line is an asynchronous copy into pinned memory plus an event, and lines are written, in order, as soon
         # as the head of the queue is ready -- at the latest by flush_log() / exit() / the next blocking point.  The text and the
         # order of the lines are the reference's; only the moment they appear moves.  `async_log=False` reads and prints at once.
-        want_async = getattr(args, "async_log", None)
-        if want_async is None:
-            want_async = os.environ.get("FLY_ASYNC_LOG", "1") != "0"
-        self._async_log = bool(want_async) and dev.type == "cuda"
+        self._async_log = opts.async_log and dev.type == "cuda"
         self._log_q = collections.deque()
         # opt-in (`--log_throughput`): the score line also carries env-steps/s (all ranks) over the steps since the previous score
         # line, by the host's clock.  Off by default: stdout then is the reference's lines (ppo.py:257-260), character for character.
-        self.log_throughput = bool(getattr(args, "log_throughput", False))
+        self.log_throughput = opts.log_throughput
         self._rate_mark = None                                      # (perf_counter, run_step) of the previous score line
         self._pending_step = None                                   # deferred check of the device step counter (_update_hip)
         self._in_run_tail = False                                   # True inside run()'s periodic save (save_training_state)
@@ -274,24 +254,19 @@ class PPO:
 
         self.net = Net(self.env.num_obs, self.env.num_act).to(dev)
         loaded_rms, loaded_value_rms = {}, {}
-        if self._resume_state is not None:                          # the weights file, as `load` below takes it
-            print("resuming from: ", str(self.args.resume_path))
-            sd = torch.load(self.args.resume_path, map_location=dev, weights_only=True)
+        if opts.resume or opts.load:                                # ppo.py:147-149; a resumed run's weights file goes in alike
+            said, path = ("resuming from: ", opts.resume_path) if opts.resume else ("loaded from: ", self.args.load_path)
+            print(said, str(path))
+            sd = torch.load(path, map_location=dev, weights_only=True)
             loaded_rms = split_obs_rms(sd, self.normalize_obs)
             loaded_value_rms = split_value_rms(sd, self.normalize_value)
             self.net.load_state_dict(sd)
-        if getattr(self.args, "load", False):                       # ppo.py:147-149
-            print("loaded from: ", str(self.args.load_path))
-            sd = torch.load(self.args.load_path, map_location=dev, weights_only=True)
-            loaded_rms = split_obs_rms(sd, self.normalize_obs)
-            loaded_value_rms = split_value_rms(sd, self.normalize_value)
-            self.net.load_state_dict(sd)
-        self._loaded = bool(getattr(self.args, "load", False))
+        self._loaded = opts.load
         from .policy import PackedPolicy
         self.policy = PackedPolicy(self.net, dev)                   # parameters become views of one packed buffer
         self.net._policy = self.policy
         # "hip": MFMA forward/backward + fused clip/Adam kernels; "torch": torch-ROCm autograd (A/B reference)
-        self.update_backend = getattr(args, "update_backend", "hip")
+        self.update_backend = opts.update_backend
         self.policy.init_training(self.mini_chunk_size * n, lr=self.lr)
         action_var = 0.01 if self.args.testing else 0.2             # ppo.py:152
         # ppo.py:236-237 decays the variance after every env step and ppo.py:233 adds the step's mean
@@ -311,24 +286,38 @@ class PPO:
         if self.normalize_value:
             self._setup_value_norm(loaded_value_rms)
         self._gen = torch.Generator(device=dev)
-        self._gen.manual_seed(int(getattr(args, "seed", 0)) + 1000003 * int(getattr(args, "rank", 0)))
-        self.world_size = int(getattr(args, "world_size", 1))
+        self._gen.manual_seed(opts.seed + 1000003 * opts.rank)
+        self.world_size = opts.world_size
         # "grad_allreduce" (default): one packed-gradient all-reduce per optimizer step = the reference's
         # update on the global minibatch.  "param_average": one exchange per PPO update (non-parity).
-        self.dp_mode = getattr(args, "dp_mode", "grad_allreduce")
-        if self.dp_mode not in ("grad_allreduce", "param_average"):
-            raise ValueError("dp_mode must be grad_allreduce or param_average")
+        self.dp_mode = opts.dp_mode
         # the per-step gradient exchange: "rccl" = torch.distributed.all_reduce (RCCL over xGMI; the default and the
         # fallback) or "p2p" = the one-shot peer-to-peer kernel of csrc/dp_p2p.hip (one node, <= 16 ranks)
         # "auto" = p2p if its start-up self-test against the collective passes on this node, else rccl.
-        self.dp_allreduce = getattr(args, "dp_allreduce", None) or os.environ.get("FLY_DP_ALLREDUCE", "rccl")
-        if self.dp_allreduce not in ("rccl", "p2p", "auto"):
-            raise ValueError("dp_allreduce must be rccl, p2p or auto")
+        self.dp_allreduce = opts.dp_allreduce
         self._p2p = None
         self._flat_grad = None
         if self.world_size > 1:
             from .dist import FlatGradAllReduce
             self._flat_grad = FlatGradAllReduce(self.net.parameters(), self.world_size)
+
+    def _say_no_statistics(self, option, what):
+        """The line for a loaded weights file without the statistics that `option` keeps (none for a new network)."""
+        if self._loaded:
+            print("%s: %s holds no %s; starting from mean 0, var 1" % (option, str(self.args.load_path), what))
+
+    def _all_rank_sets(self, sets, keep):
+        """The moment sets of every rank, in rank order, on the device (one rank: `sets` itself).  A gloo group gathers on the
+        CPU; the gathered tensor is held in the attribute `keep` until the stream has consumed it."""
+        if self.world_size == 1:
+            return sets
+        import torch.distributed as dist
+        src = sets.cpu() if dist.get_backend() == "gloo" else sets
+        parts = [torch.empty_like(src) for _ in range(self.world_size)]
+        dist.all_gather(parts, src)
+        sets = torch.cat(parts).to(self.device)
+        setattr(self, keep, sets)
+        return sets
 
     # ------------------------------------------------------------------------------------------
     # observation normalisation (opt-in)
@@ -344,9 +333,8 @@ class PPO:
             self._obs_stats[0] = loaded_rms["obs_rms.count"].to(dev, torch.float64).reshape(())
             self._obs_stats[1:1 + k] = loaded_rms["obs_rms.mean"].to(dev, torch.float64)
             self._obs_stats[1 + k:] = loaded_rms["obs_rms.var"].to(dev, torch.float64)
-        elif getattr(self.args, "load", False):
-            print("normalize_obs: %s holds no observation statistics (obs_rms.*); starting from mean 0, var 1"
-                  % str(self.args.load_path))
+        else:
+            self._say_no_statistics("normalize_obs", "observation statistics (obs_rms.*)")
         self._obs_table = torch.empty(_lib.OBS_NORM_SET, dtype=torch.float32, device=dev)
         self._obs_table.copy_(obs_norm_table(self._obs_stats, self.obs_clip))
         self._obs_norm_ring = torch.empty_like(self._obs_ring)
@@ -374,21 +362,12 @@ class PPO:
         float64 moments of rows 1..T (the observations this rollout produced; row 0 is the previous rollout's row T) into
         _obs_sets.  Idempotent until the next merge."""
         T, n = self.rollout_size, int(self.args.num_envs)
-        p = lambda x: C.c_void_p(x.data_ptr())   # noqa: E731
         _lib.check(self._lib.ppo_obs_norm_pass(p(self._obs_ring), C.c_int64((T + 1) * n), C.c_int64(n), p(self._obs_table),
                                                p(self._obs_norm_ring), p(self._obs_sets), _lib.stream_ptr()), "ppo_obs_norm_pass")
 
     def _merge_obs_stats(self):
         """Fold the moments of the last pass into S (all ranks' sets, in rank order) and rewrite the table: S_k -> S_k+1."""
-        sets = self._obs_sets
-        if self.world_size > 1:
-            import torch.distributed as dist
-            src = sets.cpu() if dist.get_backend() == "gloo" else sets
-            parts = [torch.empty_like(src) for _ in range(self.world_size)]
-            dist.all_gather(parts, src)
-            sets = torch.cat(parts).to(self.device)
-            self._keep_sets = sets                                  # alive until the stream has consumed it
-        p = lambda x: C.c_void_p(x.data_ptr())   # noqa: E731
+        sets = self._all_rank_sets(self._obs_sets, "_keep_sets")
         _lib.check(self._lib.ppo_obs_norm_merge(p(self._obs_stats), p(self._obs_table), p(sets), C.c_int64(sets.shape[0]),
                                                 C.c_float(self.obs_clip), _lib.stream_ptr()), "ppo_obs_norm_merge")
 
@@ -404,9 +383,8 @@ class PPO:
         if loaded_rms:
             for i, k in enumerate(("value_rms.count", "value_rms.mean", "value_rms.var")):
                 self._value_stats[i] = loaded_rms[k].to(dev, torch.float64).reshape(())
-        elif getattr(self.args, "load", False):
-            print("normalize_value: %s holds no value statistics (value_rms.*); starting from mean 0, var 1"
-                  % str(self.args.load_path))
+        else:
+            self._say_no_statistics("normalize_value", "value statistics (value_rms.*)")
         self._value_table = value_norm_table(self._value_stats).contiguous()
         self._value_stats_next = self._value_stats.clone()
         self._value_table_next = self._value_table.clone()
@@ -442,7 +420,6 @@ class PPO:
         targets normalised under the scratch table (ppo_value_norm_apply).  Nothing committed is written, so it is idempotent
         on a finished rollout."""
         T, n = self.rollout_size, int(self.args.num_envs)
-        p = lambda x: C.c_void_p(x.data_ptr())   # noqa: E731
         if self.gae == "episodic":
             _lib.check(self._lib.ppo_td_gae_episodic_vnorm(
                 p(self.all_reward), p(values[:T]), p(values[1:]), p(self._reset_rows), p(self._progress_rows),
@@ -454,14 +431,7 @@ class PPO:
                 p(self.all_reward), p(values[:T]), p(values[1:]), p(done_f), p(self._value_table), C.c_float(self.gamma),
                 C.c_float(self.lmbda), C.c_int64(T), C.c_int64(n), p(self._target), p(self.all_advantage), p(self._value_sets),
                 C.c_int(mode), _lib.stream_ptr()), "ppo_td_gae_vnorm")
-        sets = self._value_sets
-        if self.world_size > 1:
-            import torch.distributed as dist
-            src = sets.cpu() if dist.get_backend() == "gloo" else sets
-            parts = [torch.empty_like(src) for _ in range(self.world_size)]
-            dist.all_gather(parts, src)
-            sets = torch.cat(parts).to(self.device)
-            self._keep_value_sets = sets                            # alive until the stream has consumed it
+        sets = self._all_rank_sets(self._value_sets, "_keep_value_sets")
         _lib.check(self._lib.ppo_value_norm_merge(p(self._value_stats), p(sets), C.c_int64(sets.shape[0]),
                                                   p(self._value_stats_next), p(self._value_table_next), _lib.stream_ptr()),
                    "ppo_value_norm_merge")
@@ -477,14 +447,11 @@ class PPO:
     # shuffled minibatches (opt-in)
     def _setup_minibatch(self):
         """The one staging minibatch (obs | action | log-prob | target | advantage rows, 376 B per row: 15.4 MB at the default
-        shape; stream order makes one set enough), this rank's seed (`minibatch_seed`, default `seed`, + rank * 0x9E3779B9
-        wrapping, as domain randomisation) and the count of update() calls the epoch keys are derived from.  Nothing of it goes
-        into the weights file; `--save_state` carries it."""
+        shape; stream order makes one set enough), this rank's seed (options.py: `minibatch_seed`, default `seed`, offset by
+        the rank as domain randomisation's) and the count of update() calls the epoch keys are derived from.  Nothing of it
+        goes into the weights file; `--save_state` carries it."""
         dev, rows = self.device, self.mini_chunk_size * int(self.args.num_envs)
-        seed = getattr(self.args, "minibatch_seed", None)
-        if seed is None:
-            seed = getattr(self.args, "seed", 0)
-        self._mb_seed = (int(seed) + int(getattr(self.args, "rank", 0)) * 0x9E3779B9) & 0xFFFFFFFF
+        self._mb_seed = self.options.minibatch_seed
         self._mb_update = 0
         self._mb_stage = (torch.zeros((rows, self.num_obs), device=dev), torch.zeros((rows, self.num_acts), device=dev),
                           torch.zeros(rows, device=dev), torch.zeros((rows, 1), device=dev), torch.zeros((rows, 1), device=dev))
@@ -497,7 +464,6 @@ class PPO:
         [rows], tests) receives the source rows."""
         T, n = self.rollout_size, int(self.args.num_envs)
         so, sa, sl, st, sv = self._mb_stage
-        p = lambda x: C.c_void_p(x.data_ptr())   # noqa: E731
         _lib.check(self._lib.ppo_minibatch_gather(
             p(obs), p(action), p(old_log_prob), p(advantage), p(target), C.c_int64(T * n), C.c_uint32(self._mb_seed),
             C.c_uint32(epoch_key & 0xFFFFFFFF), C.c_int64(first), C.c_int64(rows), p(so), p(sa), p(sl), p(sv), p(st),
@@ -549,7 +515,6 @@ class PPO:
     def _td_gae_episodic(self, values, mode):
         """make_data's GAE pass with gae='episodic' (ppo_td_gae_episodic): straight from the int64 flag rows, no conversions."""
         T, n = self.rollout_size, int(self.args.num_envs)
-        p = lambda x: C.c_void_p(x.data_ptr())   # noqa: E731
         _lib.check(self._lib.ppo_td_gae_episodic(
             p(self.all_reward), p(values[:T]), p(values[1:]), p(self._reset_rows), p(self._progress_rows), p(self._ended_prev),
             C.c_int64(self.env.max_episode_length), C.c_float(self.gamma), C.c_float(self.lmbda), C.c_int64(T), C.c_int64(n),
@@ -558,8 +523,7 @@ class PPO:
     # ------------------------------------------------------------------------------------------
     @property
     def action_var(self):
-        if getattr(self, "_book_terms", None) is not None:
-            self._flush_bookkeeping()
+        self._flush_bookkeeping()
         return self._action_var
 
     @action_var.setter
@@ -582,7 +546,10 @@ class PPO:
             self._action_var.copy_(v.expand_as(self._action_var))
 
     def _flush_bookkeeping(self):
-        """Apply the score terms and variance decays of rollout rows [_book_from, _rows_done)."""
+        """Apply the score terms and variance decays of rollout rows [_book_from, _rows_done); there are none before the first
+        step has built the launch arguments (`_book_terms`, _prepare_step_args)."""
+        if self._book_terms is None:
+            return
         rows = self._rows_done - self._book_from
         if rows <= 0:
             return
@@ -611,34 +578,26 @@ class PPO:
             else:
                 values = self.net.v(ring)                           # [T+1, N, 1]: v(obs) and v(next_obs) in one pass
             self._v_have = 0
+            mode = 4 if n < 512 and T >= 1024 else 0                # PPO_GAE_SCAN: few envs x long rollout
             if self.gae == "episodic":
-                mode = 4 if n < 512 and T >= 1024 else 0            # the same rule: PPO_GAE_SCAN for few envs x long rollout
                 if self.normalize_value:
                     self._td_gae_vnorm(values, None, mode)
                 else:
                     self._td_gae_episodic(values, mode)
                 self._keep = (values,)
-                if self.normalize_advantage:
-                    self._normalize_advantage()
-                obs = self._obs_norm_ring[:T] if self.normalize_obs else self.all_obs
-                target = self._target_norm if self.normalize_value else self._target
-                return obs, self.all_acts, self.all_log_prob, target, self.all_advantage
-            done = self.all_done
-            per_step = done.dim() == 3 and done.shape[0] == T and done.shape[1] == n
-            mode = 1 if per_step else 0                             # reference path: [N,1]
-            if n < 512 and T >= 1024:
-                mode |= 4                                           # PPO_GAE_SCAN: few envs x long rollout
-            done_f = done.to(torch.float32).contiguous()
-            if self.normalize_value:
-                self._td_gae_vnorm(values, done_f, mode)            # `values` are normalised-unit outputs: denormalised there
             else:
-                _lib.check(self._lib.ppo_td_gae(
-                    C.c_void_p(self.all_reward.data_ptr()), C.c_void_p(values[:T].data_ptr()),
-                    C.c_void_p(values[1:].data_ptr()), C.c_void_p(done_f.data_ptr()),
-                    C.c_float(self.gamma), C.c_float(self.lmbda), C.c_int64(T), C.c_int64(n),
-                    C.c_void_p(self._target.data_ptr()), C.c_void_p(self.all_advantage.data_ptr()),
-                    C.c_int(mode), _lib.stream_ptr()), "ppo_td_gae")
-            self._keep = (values, done_f)                           # alive until the stream has consumed them
+                done = self.all_done
+                if done.dim() == 3 and done.shape[0] == T and done.shape[1] == n:
+                    mode |= 1                                       # per-step mask; the reference path is [N,1]
+                done_f = done.to(torch.float32).contiguous()
+                if self.normalize_value:
+                    self._td_gae_vnorm(values, done_f, mode)        # `values` are normalised-unit outputs: denormalised there
+                else:
+                    _lib.check(self._lib.ppo_td_gae(
+                        p(self.all_reward), p(values[:T]), p(values[1:]), p(done_f), C.c_float(self.gamma),
+                        C.c_float(self.lmbda), C.c_int64(T), C.c_int64(n), p(self._target), p(self.all_advantage),
+                        C.c_int(mode), _lib.stream_ptr()), "ppo_td_gae")
+                self._keep = (values, done_f)                       # alive until the stream has consumed them
             if self.normalize_advantage:
                 self._normalize_advantage()
         obs = self._obs_norm_ring[:T] if self.normalize_obs else self.all_obs
@@ -650,7 +609,6 @@ class PPO:
         ALL ranks.  Not in the reference (ppo.py:171 uses raw advantages); named by BASELINE's north_star."""
         import torch.distributed as dist
         cnt = self.all_advantage.numel()
-        p = lambda x: C.c_void_p(x.data_ptr())   # noqa: E731
         _lib.check(self._lib.ppo_adv_stats(p(self.all_advantage), C.c_int64(cnt), p(self._adv_stats), _lib.stream_ptr()),
                    "ppo_adv_stats")
         if self.world_size > 1:
@@ -678,8 +636,7 @@ class PPO:
         """ppo.py:173-202: 5 epochs x 15 contiguous-in-T minibatches; the 16th chunk is never
         visited (Q3).  With world_size > 1 the flat gradient is all-reduced (mean) before the clip.
         minibatch='shuffled': the same 75 steps on windows of a fresh permutation of all rows per epoch."""
-        if getattr(self, "_book_terms", None) is not None:
-            self._flush_bookkeeping()                               # the loss uses the variance after this rollout's decays
+        self._flush_bookkeeping()                                   # the loss uses the variance after this rollout's decays
         obs, action, old_log_prob, target, advantage = self.make_data()
         if self.update_backend == "hip":
             self._update_hip(obs, action, old_log_prob, target, advantage)
@@ -770,7 +727,7 @@ class PPO:
                 dist.all_reduce(word, op=dist.ReduceOp.MAX)
                 if int(word.item()) != 0:
                     if failed is not None:
-                        print("rank %d: %s; every rank runs this update on bf16x3" % (int(getattr(self.args, "rank", 0)), failed))
+                        print("rank %d: %s; every rank runs this update on bf16x3" % (self.options.rank, failed))
                     pol.h2_suspended = cal_failed = True        # cleared at the end of this update, below
                     pol.h2_calibrated = False
                     pol.h2_calibration_failures += 1
@@ -882,7 +839,7 @@ class PPO:
         if good:
             flag = torch.ones(1, device=self.device, dtype=torch.int32)
             gen = torch.Generator(device=self.device)
-            gen.manual_seed(7 + int(getattr(self.args, "rank", 0)))
+            gen.manual_seed(7 + self.options.rank)
             for _ in range(3):
                 a = torch.randn(n, device=self.device, generator=gen)
                 a[ERR_SLOT] = 0.0
@@ -903,7 +860,7 @@ class PPO:
             p2p.close()
         if self.dp_allreduce == "p2p":
             raise _lib.FlyHipError("dp_allreduce=p2p is not usable on this node: %s" % (why or "a peer failed"))
-        if int(getattr(self.args, "rank", 0)) == 0:
+        if self.options.rank == 0:
             print("dp_allreduce auto: peer-to-peer all-reduce unavailable (%s); using the RCCL collective" % (why or "a peer failed"))
         self.dp_allreduce = "rccl"
         return None
@@ -1059,7 +1016,7 @@ class PPO:
     def _emit_score(self):
         """ppo.py:257-260: the score line of this step.  Values are read from the device asynchronously (pinned memory + event);
         the accumulator is cleared on the stream, behind the copy."""
-        rank0 = int(getattr(self.args, "rank", 0)) == 0
+        rank0 = self.options.rank == 0
         suffix = self._throughput_suffix()
         if not self._async_log:
             self._drain_log(block=True)
@@ -1204,7 +1161,7 @@ class PPO:
         if not getattr(self.args, "save", False):
             return
         self._check_step_counter()
-        rank = int(getattr(self.args, "rank", 0))
+        rank = self.options.rank
         path = self.args.save_path + endofname + ".pth"
         if rank == 0:
             # parameters are views of the packed buffer: save compact, contiguous copies
@@ -1249,8 +1206,7 @@ class PPO:
         if self.update_backend != "hip":
             raise ValueError("save_training_state: update_backend=%r keeps its optimizer state in torch.optim.Adam, which is not "
                              "part of a training state" % (self.update_backend,))
-        if getattr(self, "_book_terms", None) is not None:
-            self._flush_bookkeeping()
+        self._flush_bookkeeping()
         self._check_step_counter()
         self.flush_log()
         run_step = self.run_step
@@ -1288,9 +1244,9 @@ class PPO:
             state = self._resume_state
         else:
             if path is None:
-                if getattr(self.args, "resume_path", None) is None:
+                if self.options.resume_path is None:
                     raise ValueError("load_training_state: no path given and no args.resume_path")
-                path = self.training_state_path(self.args.resume_path, int(getattr(self.args, "rank", 0) or 0))
+                path = self.training_state_path(self.options.resume_path, self.options.rank)
             state = train_state.read_state_file(path)
         self._resume_state = None
         if self.mini_batch_number != 0:
@@ -1311,8 +1267,7 @@ class PPO:
         self.policy.load_training_state(train_state.block(state, "policy"))
         self.env.load_training_state(train_state.block(state, "env"))
         self.run_step, self.optim_step = value(agent, "agent", "run_step", int), value(agent, "agent", "optim_step", int)
-        if getattr(self, "_book_terms", None) is not None:
-            self._flush_bookkeeping()                               # (an agent that has run: nothing pending on the old variance)
+        self._flush_bookkeeping()                                   # (an agent that has run: nothing pending on the old variance)
         restore(self._action_var, agent, "agent", "action_var")
         restore(self._score_acc, agent, "agent", "score_acc")
         gen = self._gen.get_state()

@@ -15,9 +15,9 @@ import os
 
 import torch
 
+from . import options
+
 FORMAT = 1
-MINI_BATCH_SIZE, CHUNK_NUMBER = 40960, 16           # ppo.py:118-121: rollout_size = (40960 // num_envs) * 16
-MAX_PERSISTENT_ROLLOUT = 4096                       # one launch per rollout up to this many steps (PPO.persistent_rollout)
 
 META_FIELDS = ("num_envs", "rollout_size", "variant", "reward", "world_size", "rank", "gae", "minibatch", "minibatch_seed",
                "action_noise", "noise_rho", "normalize_obs", "obs_clip", "normalize_value", "normalize_advantage", "randomize",
@@ -32,57 +32,16 @@ def training_state_path(weights_path, rank):
 
 
 def resolve_gemm(args):
-    """(gemm, step_gemm) as PackedPolicy starts with them ($FLY_GEMM, $FLY_STEP_GEMM) and `trainer.main` then sets them from
-    `--gemm`: what `policy.gemm` / `policy.step_gemm` report once the run is set up."""
-    env_gemm = os.environ.get("FLY_GEMM")
-    gemm = "bf16x3" if env_gemm in (None, "f16x2") else env_gemm
-    step = os.environ.get("FLY_STEP_GEMM", "f16x2" if env_gemm in (None, "f16x2") else "bf16x3")
-    want = getattr(args, "gemm", None)
-    if want == "f16x2":
-        gemm, step = "bf16x3", "f16x2"
-    elif want:
-        gemm, step = want, "bf16x3"
-    return gemm, (step if gemm == "bf16x3" else gemm)
+    """(gemm, step_gemm) as `policy.gemm` / `policy.step_gemm` report them once the run that `args` describes is set up
+    (options.resolve_gemm has the rule)."""
+    return options.resolve_gemm(options.wanted_gemm(args), os.environ)
 
 
 def expected_meta(args):
     """The meta block of the run that `args` describes, from the args (and the environment variables the options default to)
-    alone.  An option that is off stores None for its dependent values (`noise_rho` without ar1, `obs_clip` without
-    normalize_obs, the seeds and ranges of features that are off): they mean nothing then, and must not block a resume."""
-    from .fly import DR_NAMES, dr_args
-    n = int(args.num_envs)
-    rank = int(getattr(args, "rank", 0) or 0)
-    T = (MINI_BATCH_SIZE // n) * CHUNK_NUMBER
-    minibatch = getattr(args, "minibatch", "reference")
-    mb_seed = None
-    if minibatch == "shuffled":
-        mb_seed = getattr(args, "minibatch_seed", None)
-        if mb_seed is None:
-            mb_seed = getattr(args, "seed", 0)
-        mb_seed = (int(mb_seed) + rank * 0x9E3779B9) & 0xFFFFFFFF
-    action_noise = getattr(args, "action_noise", "white")
-    normalize_obs = bool(getattr(args, "normalize_obs", False))
-    randomize = bool(getattr(args, "randomize", False))
-    dr_ranges = dr_seed = None
-    if randomize:
-        ranges, dr_seed = dr_args(args)
-        dr_ranges = [[float(ranges[k][0]), float(ranges[k][1])] for k in DR_NAMES]
-    want = getattr(args, "persistent_rollout", None)
-    if want is None:
-        want = os.environ.get("FLY_PERSISTENT_ROLLOUT", "1") != "0"
-    gemm, step_gemm = resolve_gemm(args)
-    return {
-        "num_envs": n, "rollout_size": T, "variant": getattr(args, "variant", "bigGrav"),
-        "reward": getattr(args, "reward", "standing"), "world_size": int(getattr(args, "world_size", 1)), "rank": rank,
-        "gae": getattr(args, "gae", "reference"), "minibatch": minibatch, "minibatch_seed": mb_seed,
-        "action_noise": action_noise, "noise_rho": float(getattr(args, "noise_rho", 0.5)) if action_noise == "ar1" else None,
-        "normalize_obs": normalize_obs, "obs_clip": float(getattr(args, "obs_clip", 5.0)) if normalize_obs else None,
-        "normalize_value": bool(getattr(args, "normalize_value", False)),
-        "normalize_advantage": bool(getattr(args, "normalize_advantage", False)),
-        "randomize": randomize, "dr_ranges": dr_ranges, "dr_seed": dr_seed, "gemm": gemm, "step_gemm": step_gemm,
-        "persistent_rollout": bool(want) and T <= MAX_PERSISTENT_ROLLOUT and not bool(getattr(args, "graph", False)),
-        "dp_mode": getattr(args, "dp_mode", "grad_allreduce"),
-    }
+    alone: the resolved record (options.resolve), projected onto META_FIELDS."""
+    meta = options.projection(options.resolve(args, os.environ))
+    return {field: meta[field] for field in META_FIELDS}
 
 
 def compare_meta(file_meta, run_meta):

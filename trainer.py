@@ -50,83 +50,94 @@ import torch
 
 
 def parse_args(argv=None):
+    from fly_bproject_amd import options as O
     parser = argparse.ArgumentParser()
-    parser.add_argument('--sim_device', type=str, default="cuda:0", help='Physics Device in PyTorch-like syntax')
-    parser.add_argument('--rl_device', type=str, default=None, help='accepted for compatibility; sim_device is used')
-    parser.add_argument('--compute_device_id', default=0, type=int)
-    parser.add_argument('--graphics_device_id', type=int, default=0, help='Graphics Device ID')
-    parser.add_argument('--num_envs', default=1000, type=int)
-    parser.add_argument('--headless', default=False)
-    parser.add_argument('--save', type=bool, default=False)
-    parser.add_argument('--save_path', type=str, default=None)
-    parser.add_argument('--save_freq', type=int, default=100)
-    parser.add_argument('--load', type=bool, default=False)
-    parser.add_argument('--load_path', type=str, default=None)
-    parser.add_argument('--record', type=bool, default=False)
-    parser.add_argument('--record_dir_name', type=str, default=None)
-    parser.add_argument('--time_steps_per_recorded_frame', type=int, default=2)
-    parser.add_argument('--testing', type=bool, default=False)
-    parser.add_argument('--variant', type=str, default="bigGrav", choices=["bigGrav", "lowGrav"])
-    parser.add_argument('--reward', type=str, default="standing", choices=["standing", "walking"])
-    parser.add_argument('--max_steps', type=int, default=0, help='stop after this many env steps (0 = run until env.end)')
-    parser.add_argument('--seed', type=int, default=0)
-    parser.add_argument('--gemm', type=str, default=None, choices=["f32", "bf16x3", "f16x2"],
-                        help='arithmetic of the MLP GEMMs: f16x2 (default) = bf16x3 for the rollout policy and the critic pass, the '
-                             'optimizer-step gradient in the two-term fp16 split with three product terms and per-class '
-                             'power-of-two scales (DESIGN.md 3.4c; a step whose values do not fit fp16 is refused on the device '
-                             'and redone in bf16x3); bf16x3 = fp32 operands split exactly into three bf16 terms on the bf16 matrix '
-                             'pipe, fp32 accumulate, for EVERY GEMM (DESIGN.md 3.4); f32 = v_mfma_f32_32x32x2_f32.  All are held to '
-                             'the reference goldens at the fp32 tolerances.  Default: $FLY_GEMM or f16x2')
-    parser.add_argument('--log_throughput', action='store_true',
-                        help='append env-steps/s (all ranks, host clock, since the previous score line) to the score line '
-                             '(ppo.py:257-260 prints the score only; off by default so that stdout stays the reference\'s)')
-    parser.add_argument('--dp_mode', type=str, default="grad_allreduce", choices=["grad_allreduce", "param_average"],
-                        help='multi-GPU: all-reduce the gradient every optimizer step (reference algorithm on the global '
-                             'batch) or average parameters once per PPO update (non-parity)')
-    parser.add_argument('--normalize_advantage', action='store_true',
-                        help='normalise advantages over the rollout (not in the reference; off by default)')
-    parser.add_argument('--normalize_obs', action='store_true',
-                        help='normalise the policy input by running mean / std of the observations, clamped to +-obs_clip '
-                             '(rl_games normalize_input; not in the reference; off by default)')
-    parser.add_argument('--normalize_value', action='store_true',
-                        help='the critic regresses on TD targets normalised by their running mean / std, and its outputs are '
-                             'mapped back to reward units for the TD target and GAE (rl_games normalize_value, without its clamp; '
-                             'not in the reference; off by default)')
-    parser.add_argument('--gae', type=str, default="reference", choices=["reference", "episodic"],
-                        help='advantage estimator: reference = ppo.py:157-171 as it stands (the done mask of the last step over the '
-                             'whole rollout, no reset of the recurrence at episode ends); episodic = per-step end flags, the '
-                             'recurrence stops at every episode end, time-outs bootstrap from the value of the next observation '
-                             '(rl_games value_bootstrap / time_outs) and the step that performs a reset trains nothing.  episodic '
-                             'is NOT the reference\'s estimator; off by default')
-    parser.add_argument('--minibatch', type=str, default="reference", choices=["reference", "shuffled"],
-                        help='minibatches of the update: reference = ppo.py:173-202 as it stands (15 contiguous-in-time slices of the '
-                             'rollout, the same in every epoch; the 16th chunk trains nothing); shuffled = every epoch cuts its 15 '
-                             'minibatches from a fresh keyed permutation of all rows of the rollout (still 75 optimizer steps per '
-                             'update; each epoch leaves a random sixteenth out).  shuffled is NOT the reference\'s update; off by default')
-    parser.add_argument('--minibatch_seed', type=int, default=None, help='seed of the minibatch permutations (default: --seed)')
-    parser.add_argument('--action_noise', type=str, default="white", choices=["white", "ar1"],
-                        help='exploration noise of the rollout: white = ppo.py:215-220 as it stands (an independent N(0, 1) draw per '
-                             'step and joint); ar1 = the draws of a rollout are filtered along time into an AR(1) process with unit '
-                             'stationary variance (each step still N(0, 1), corr(t, t + k) = rho^k; continuous across rollouts, not '
-                             'restarted at episode ends).  ar1 is NOT the reference\'s sampling; off by default')
-    parser.add_argument('--noise_rho', type=float, default=0.5,
-                        help='lag-1 correlation of --action_noise ar1, 0 < rho < 1 (0.5: between white and pink noise, a starting '
-                             'choice, not a measurement)')
-    parser.add_argument('--obs_clip', type=float, default=5.0, help='bound of a normalised observation (with --normalize_obs)')
-    parser.add_argument('--randomize', action='store_true',
-                        help='per-env physics domain randomisation, redrawn at every reset of the env (Isaac Gym actor-property '
-                             'randomisation; not in the reference; off by default)')
-    from fly_bproject_amd.fly import DR_DEFAULT_RANGES, DR_NAMES
-    for name in DR_NAMES:
-        parser.add_argument('--dr_' + name, type=float, nargs=2, default=list(DR_DEFAULT_RANGES[name]), metavar=('LO', 'HI'),
-                            help='range of the %s multiplier (with --randomize; mass scales the inertia too)' % name)
-    parser.add_argument('--dr_seed', type=int, default=None, help='seed of the randomisation draws (default: --seed)')
-    parser.add_argument('--save_state', action='store_true',
-                        help='with --save_path: every save at a rollout boundary also writes <save_path><suffix>.state.r<rank>.pth, '
-                             'the full training state of each rank, for --resume_path (off by default: the weights file alone)')
-    parser.add_argument('--resume_path', type=str, default=None,
-                        help='a weights file written by a --save_state run: continue that run bit for bit from it and the state '
-                             'files beside it, under the same options (excludes --load_path and --testing)')
+
+    def flag(name, **kw):
+        """--<name>, its default and choices from the one table of options."""
+        opt = O.BY_NAME[name]
+        if opt.choices:
+            kw['choices'] = list(opt.choices)
+        if kw.get('action') != 'store_true':
+            default = O.flag_default(name)
+            kw['default'] = list(default) if isinstance(default, tuple) else default
+        parser.add_argument('--' + name, **kw)
+
+    flag('sim_device', type=str, help='Physics Device in PyTorch-like syntax')
+    flag('rl_device', type=str, help='accepted for compatibility; sim_device is used')
+    flag('compute_device_id', type=int)
+    flag('graphics_device_id', type=int, help='Graphics Device ID')
+    flag('num_envs', type=int)
+    flag('headless')
+    flag('save', type=bool)
+    flag('save_path', type=str)
+    flag('save_freq', type=int)
+    flag('load', type=bool)
+    flag('load_path', type=str)
+    flag('record', type=bool)
+    flag('record_dir_name', type=str)
+    flag('time_steps_per_recorded_frame', type=int)
+    flag('testing', type=bool)
+    flag('variant', type=str)
+    flag('reward', type=str)
+    flag('max_steps', type=int, help='stop after this many env steps (0 = run until env.end)')
+    flag('seed', type=int)
+    flag('gemm', type=str,
+         help='arithmetic of the MLP GEMMs: f16x2 (default) = bf16x3 for the rollout policy and the critic pass, the '
+              'optimizer-step gradient in the two-term fp16 split with three product terms and per-class '
+              'power-of-two scales (DESIGN.md 3.4c; a step whose values do not fit fp16 is refused on the device '
+              'and redone in bf16x3); bf16x3 = fp32 operands split exactly into three bf16 terms on the bf16 matrix '
+              'pipe, fp32 accumulate, for EVERY GEMM (DESIGN.md 3.4); f32 = v_mfma_f32_32x32x2_f32.  All are held to '
+              'the reference goldens at the fp32 tolerances.  Default: $FLY_GEMM or f16x2')
+    flag('log_throughput', action='store_true',
+         help='append env-steps/s (all ranks, host clock, since the previous score line) to the score line '
+              '(ppo.py:257-260 prints the score only; off by default so that stdout stays the reference\'s)')
+    flag('dp_mode', type=str,
+         help='multi-GPU: all-reduce the gradient every optimizer step (reference algorithm on the global '
+              'batch) or average parameters once per PPO update (non-parity)')
+    flag('normalize_advantage', action='store_true',
+         help='normalise advantages over the rollout (not in the reference; off by default)')
+    flag('normalize_obs', action='store_true',
+         help='normalise the policy input by running mean / std of the observations, clamped to +-obs_clip '
+              '(rl_games normalize_input; not in the reference; off by default)')
+    flag('normalize_value', action='store_true',
+         help='the critic regresses on TD targets normalised by their running mean / std, and its outputs are '
+              'mapped back to reward units for the TD target and GAE (rl_games normalize_value, without its clamp; '
+              'not in the reference; off by default)')
+    flag('gae', type=str,
+         help='advantage estimator: reference = ppo.py:157-171 as it stands (the done mask of the last step over the '
+              'whole rollout, no reset of the recurrence at episode ends); episodic = per-step end flags, the '
+              'recurrence stops at every episode end, time-outs bootstrap from the value of the next observation '
+              '(rl_games value_bootstrap / time_outs) and the step that performs a reset trains nothing.  episodic '
+              'is NOT the reference\'s estimator; off by default')
+    flag('minibatch', type=str,
+         help='minibatches of the update: reference = ppo.py:173-202 as it stands (15 contiguous-in-time slices of the '
+              'rollout, the same in every epoch; the 16th chunk trains nothing); shuffled = every epoch cuts its 15 '
+              'minibatches from a fresh keyed permutation of all rows of the rollout (still 75 optimizer steps per '
+              'update; each epoch leaves a random sixteenth out).  shuffled is NOT the reference\'s update; off by default')
+    flag('minibatch_seed', type=int, help='seed of the minibatch permutations (default: --seed)')
+    flag('action_noise', type=str,
+         help='exploration noise of the rollout: white = ppo.py:215-220 as it stands (an independent N(0, 1) draw per '
+              'step and joint); ar1 = the draws of a rollout are filtered along time into an AR(1) process with unit '
+              'stationary variance (each step still N(0, 1), corr(t, t + k) = rho^k; continuous across rollouts, not '
+              'restarted at episode ends).  ar1 is NOT the reference\'s sampling; off by default')
+    flag('noise_rho', type=float,
+         help='lag-1 correlation of --action_noise ar1, 0 < rho < 1 (0.5: between white and pink noise, a starting '
+              'choice, not a measurement)')
+    flag('obs_clip', type=float, help='bound of a normalised observation (with --normalize_obs)')
+    flag('randomize', action='store_true',
+         help='per-env physics domain randomisation, redrawn at every reset of the env (Isaac Gym actor-property '
+              'randomisation; not in the reference; off by default)')
+    for name in O.DR_NAMES:
+        flag('dr_' + name, type=float, nargs=2, metavar=('LO', 'HI'),
+             help='range of the %s multiplier (with --randomize; mass scales the inertia too)' % name)
+    flag('dr_seed', type=int, help='seed of the randomisation draws (default: --seed)')
+    flag('save_state', action='store_true',
+         help='with --save_path: every save at a rollout boundary also writes <save_path><suffix>.state.r<rank>.pth, '
+              'the full training state of each rank, for --resume_path (off by default: the weights file alone)')
+    flag('resume_path', type=str,
+         help='a weights file written by a --save_state run: continue that run bit for bit from it and the state '
+              'files beside it, under the same options (excludes --load_path and --testing)')
     args = parser.parse_args(argv)
     if args.save_path is not None:          # trainer.py:27-34
         args.save = True
