@@ -1,5 +1,6 @@
 """DQN variant (reference UselessFiles/dqn.py, configs[4]): oracle vs the golden vectors recorded
-from the reference's own DQN.act / DQN.update (CPU), HIP kernels vs both (GPU)."""
+from the reference's own DQN.act / DQN.update (CPU), HIP kernels vs both (GPU).
+tests/test_dqn_head_edges_gpu.py holds the head where these batches never land: all-negative Q rows, actions on a bin edge."""
 import contextlib
 import io
 
