@@ -142,6 +142,11 @@ def check(rc, what):
         raise FlyHipError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else "?"))
 
 
+def ptr(t):
+    """The device address of a tensor, as the C ABI takes it."""
+    return C.c_void_p(t.data_ptr())
+
+
 def stream_ptr():
     import torch
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)

@@ -1,7 +1,8 @@
 // dqn_layout.h — packed parameter layout of the DQN variant's Q-network (reference
 // UselessFiles/dqn.py:17-29: Linear(num_obs,256) LeakyReLU Linear(256,256) LeakyReLU Linear(256,18)),
-// mirrored by fly_bproject_amd/dqn.py.  Same conventions as mlp_layout.h: one flat fp32 buffer with every
-// layer as a row-major [N][K] matrix (K padded to a multiple of 8, N of the last layer padded to 32),
+// stated in Python by fly_bproject_amd/packing.py alone (dqn.py declares the three layers to it; tests/test_abi_cpu.py
+// compiles this header and holds packing.py's numbers to it).  Same conventions as mlp_layout.h: one flat fp32 buffer with
+// every layer as a row-major [N][K] matrix (K padded to a multiple of 8, N of the last layer padded to 32),
 // plus two derived copies in MFMA fragment order.
 //   L1  net.0  W1 [256][80]  (cols 73..79 = 0)   b1 [256]
 //   L2  net.2  W2 [256][256]                     b2 [256]

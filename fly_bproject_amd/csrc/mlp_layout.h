@@ -1,5 +1,6 @@
 // mlp_layout.h — packed parameter layout of the actor-critic network (reference ppo.py:10-102)
-// shared by the MFMA kernels (mlp_mfma.hip) and mirrored by fly_bproject_amd/policy.py.
+// shared by the MFMA kernels (mlp_mfma.hip).  fly_bproject_amd/packing.py is the one Python statement of this format
+// (policy.py declares the four layers to it); tests/test_abi_cpu.py compiles this header and holds packing.py's numbers to it.
 //
 // One flat fp32 buffer `P` (MLP_PACKED_FLOATS) holds every layer as a row-major [N][K] matrix
 // (torch's nn.Linear weight orientation), K padded to a multiple of 8 so that each lane's
@@ -29,7 +30,7 @@
 // one 128-column half of H1 in LDS at a time and accumulates layer 2 over the two k ranges.
 // Layer 4 forward (split-K over the four waves) uses
 //     ((w*4 + kq) * 64 + (h*32 + n)) * 4 + q,   w = k/32, h = (k%32)/16, kq = (k%16)/4, q = k%4.
-// fly_bproject_amd/policy.py builds the index maps; mlp_adam_step scatters every updated weight
+// fly_bproject_amd/packing.py builds the index maps; mlp_adam_step scatters every updated weight
 // into PF/PTF, so the three buffers never diverge.
 #ifndef MLP_LAYOUT_H
 #define MLP_LAYOUT_H

@@ -14,7 +14,8 @@ ABI (csrc/dqn_mfma.hip, fp32 MFMA):
   * the replay is an HBM-resident ring of whole steps (`[capacity, N, .]` tensors) instead of a Python
     deque of tuples, and a sample is a list of ring SLOTS: the kernels read the rows where they lie,
     nothing is gathered, concatenated or shuffled (the shuffle of replay.py:22 cannot change a mean).
-`Net` stays a torch module whose parameters are views into the packed buffers (checkpoints, tests).
+`Net` stays a torch module whose parameters are views into the packed buffers (checkpoints, tests); the packed
+format of csrc/dqn_layout.h is packing.py's, to which this module declares the three layers.
 
 The upstream file is stale against the current `Fly` and cannot run as written; the two repairs
 are explicit:
@@ -28,73 +29,30 @@ import random
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, packing
 from .fly import Fly
 from .params import NUM_DOF
 
+p = _lib.ptr
+
 IN, IN_PAD, H, OUT, NACT = 73, 80, 256, 32, 18
-OFF_W1 = 0
-OFF_B1 = OFF_W1 + H * IN_PAD
-OFF_W2 = OFF_B1 + H
-OFF_B2 = OFF_W2 + H * H
-OFF_W3 = OFF_B2 + H
-OFF_B3 = OFF_W3 + OUT * H
-PACKED = OFF_B3 + OUT                       # 94752 (csrc/dqn_layout.h)
-OFF_F1, OFF_F2, OFF_F3 = 0, H * IN_PAD, H * IN_PAD + H * H
-FRAG = OFF_F3 + OUT * H                     # 94208
-OFF_T3, OFF_T2 = 0, H * OUT
-FRAG_T = OFF_T2 + H * H                     # 73728
-
-
-def build_index_maps():
-    """int32 [PACKED] maps master index -> position in the forward / transposed fragment copies (-1: none)."""
-    import numpy as np
-    from .policy import _frag_index
-    idx_f = np.full(PACKED, -1, np.int32)
-    idx_t = np.full(PACKED, -1, np.int32)
-    for off_w, N, K, off_f in ((OFF_W1, H, IN_PAD, OFF_F1), (OFF_W2, H, H, OFF_F2)):
-        n, k = np.meshgrid(np.arange(N), np.arange(K), indexing="ij")
-        idx_f[off_w + n * K + k] = off_f + _frag_index(n, k, K)
-    n, k = np.meshgrid(np.arange(OUT), np.arange(H), indexing="ij")
-    w, h, kq, q = k // 64, (k % 64) // 32, (k % 32) // 4, k % 4           # layer 3 forward: split-K over the four waves
-    idx_f[OFF_W3 + n * H + k] = OFF_F3 + ((w * 8 + kq) * 64 + (h * 32 + n)) * 4 + q
-    idx_t[OFF_W3 + n * H + k] = OFF_T3 + _frag_index(k, n, OUT)           # W3^T: 256 outputs, 32 reduced
-    n, k = np.meshgrid(np.arange(H), np.arange(H), indexing="ij")
-    idx_t[OFF_W2 + n * H + k] = OFF_T2 + _frag_index(k, n, H)             # W2^T
-    for idx, size in ((idx_f, FRAG), (idx_t, FRAG_T)):
-        used = idx[idx >= 0]
-        assert len(np.unique(used)) == len(used) == size and used.max() == size - 1
-    return idx_f, idx_t
-
-
-QB_HALVES = 3 * (H * IN_PAD + H * H + OUT * H)      # 282624 (csrc/dqn_layout.h)
-QH_HALVES = 2 * (H * IN_PAD + H * H + OUT * H)      # 188416: two fp16 terms per weight (csrc/dqn_fused_h2.inc)
-QTH_HALVES = 2 * (H * OUT + H * H)                  # 147456
-QTB_HALVES = 3 * (H * OUT + H * H)                  # 221184
-OFF_QB = (0, 3 * H * IN_PAD, 3 * (H * IN_PAD + H * H))
-OFF_QTB3, OFF_QTB2 = 0, 3 * H * OUT
-
-
-def build_plane_maps():
-    """int32 [PACKED] maps master index -> term-0 position in the bf16x3 plane buffers QB / QTB (-1: no copy); terms 1 and 2
-    follow 512 and 1024 16-bit words later (csrc/dqn_layout.h, the operand order of csrc/mlp_layout.h)."""
-    import numpy as np
-    from .policy import _plane_index
-    idx_fb = np.full(PACKED, -1, np.int32)
-    idx_tb = np.full(PACKED, -1, np.int32)
-    for li, (off_w, N, K) in enumerate(((OFF_W1, H, IN_PAD), (OFF_W2, H, H), (OFF_W3, OUT, H))):
-        n, k = np.meshgrid(np.arange(N), np.arange(K), indexing="ij")
-        src = off_w + n * K + k
-        idx_fb[src] = OFF_QB[li] + _plane_index(n, k, K)
-        if li == 1:
-            idx_tb[src] = OFF_QTB2 + _plane_index(k, n, N)          # W2^T: 256 outputs, 256 reduced
-        elif li == 2:
-            idx_tb[src] = OFF_QTB3 + _plane_index(k, n, N)          # W3^T: 256 outputs, 32 reduced
-    for idx, size in ((idx_fb, QB_HALVES), (idx_tb, QTB_HALVES)):
-        used = idx[idx >= 0].astype(np.int64)
-        allpos = np.concatenate([used, used + 512, used + 1024])
-        assert len(np.unique(allpos)) == len(allpos) == size and allpos.max() == size - 1
-    return idx_fb, idx_tb
+LAYOUT = packing.Layout([
+    packing.Layer("W1", H, IN_PAD, "plain", None, "plain"),
+    packing.Layer("W2", H, H, "plain", 1, "plain"),                 # W2^T follows W3^T in the transposed buffers
+    # layer 3 forward: split-K over the four waves; its plane operand needs no order of its own (csrc/dqn_layout.h)
+    packing.Layer("W3", OUT, H, "split_k4", 0, "plain")])
+OFF_W1, OFF_W2, OFF_W3 = LAYOUT.off_w
+OFF_B1, OFF_B2, OFF_B3 = LAYOUT.off_b
+PACKED = LAYOUT.packed
+OFF_F1, OFF_F2, OFF_F3 = LAYOUT.off_f
+FRAG = LAYOUT.frag
+_, OFF_T2, OFF_T3 = LAYOUT.off_t
+FRAG_T = LAYOUT.frag_t
+QB_HALVES, QTB_HALVES = LAYOUT.pb_halves, LAYOUT.ptb_halves
+QH_HALVES, QTH_HALVES = LAYOUT.ph_halves, LAYOUT.pth_halves         # two fp16 terms per weight (csrc/dqn_fused_h2.inc)
+OFF_QB = LAYOUT.off_pb
+_, OFF_QTB2, OFF_QTB3 = LAYOUT.off_ptb
+build_index_maps, build_plane_maps = LAYOUT.index_maps, LAYOUT.plane_maps
 
 
 class Net(nn.Module):
@@ -175,43 +133,29 @@ class QNetPacked:
     kernels stream; `net` / `net_target` parameters are re-pointed at strided views of the packed buffers."""
 
     def __init__(self, net, net_target, device):
-        import numpy as np
         self.device = torch.device(device)
         z = lambda k: torch.zeros(k, dtype=torch.float32, device=self.device)   # noqa: E731
         self.P, self.PF, self.PT = z(PACKED), z(FRAG), z(FRAG_T)
         self.P_tgt, self.PF_tgt = z(PACKED), z(FRAG)
         idx_f, idx_t = build_index_maps()
-        self.idx_f = torch.from_numpy(idx_f).to(self.device)
-        self.idx_t = torch.from_numpy(idx_t).to(self.device)
-        self._src_f = torch.nonzero(self.idx_f >= 0).squeeze(-1); self._dst_f = self.idx_f[self._src_f].long()
-        self._src_t = torch.nonzero(self.idx_t >= 0).squeeze(-1); self._dst_t = self.idx_t[self._src_t].long()
-        mask = np.zeros(PACKED, np.float32)
+        self.idx_f, self._src_f, self._dst_f = packing.scatter_pairs(idx_f, self.device)
+        self.idx_t, self._src_t, self._dst_t = packing.scatter_pairs(idx_t, self.device)
         for buf, module in ((self.P, net), (self.P_tgt, net_target)):
-            views = {"net.0.weight": buf[OFF_W1:OFF_B1].view(H, IN_PAD)[:, :IN], "net.0.bias": buf[OFF_B1:OFF_W2],
-                     "net.2.weight": buf[OFF_W2:OFF_B2].view(H, H), "net.2.bias": buf[OFF_B2:OFF_W3],
-                     "net.4.weight": buf[OFF_W3:OFF_B3].view(OUT, H)[:NACT], "net.4.bias": buf[OFF_B3:OFF_B3 + NACT]}
-            params = dict(module.named_parameters())
-            assert set(params) == set(views), "Net does not have the reference's parameter set"
-            with torch.no_grad():
-                for k, view in views.items():
-                    view.copy_(params[k].data.to(self.device))
-                    params[k].data = view
+            (W1, b1), (W2, b2), (W3, b3) = LAYOUT.matrices(buf)
+            views = {"net.0.weight": W1[:, :IN], "net.0.bias": b1, "net.2.weight": W2, "net.2.bias": b2,
+                     "net.4.weight": W3[:NACT], "net.4.bias": b3[:NACT]}
+            packing.bind_parameters(module, views)
             if buf is self.P:
-                for view in views.values():
-                    idx = torch.arange(PACKED).as_strided(view.shape, view.stride(), view.storage_offset())
-                    mask[idx.reshape(-1).numpy()] = 1.0
-        self.grad_mask = torch.from_numpy(mask).to(self.device)
-        assert int(mask.sum()) == IN * H + H + H * H + H + NACT * H + NACT
+                self.grad_mask = packing.grad_mask(views, PACKED, self.device)
+        assert int(self.grad_mask.sum().item()) == IN * H + H + H * H + H + NACT * H + NACT
         self.G, self.exp_avg, self.exp_avg_sq = z(PACKED), z(PACKED), z(PACKED)
         self.step = torch.zeros(1, dtype=torch.int32, device=self.device)
         # three-term bf16 planes of the fused update (csrc/dqn_fused.inc): online forward / transposed, target forward
         zi = lambda k: torch.zeros(k, dtype=torch.int16, device=self.device)   # noqa: E731
         self.QB, self.QTB, self.QB_tgt = zi(QB_HALVES), zi(QTB_HALVES), zi(QB_HALVES)
         idx_fb, idx_tb = build_plane_maps()
-        self.idx_fb = torch.from_numpy(idx_fb).to(self.device)
-        self.idx_tb = torch.from_numpy(idx_tb).to(self.device)
-        self._src_fb = torch.nonzero(self.idx_fb >= 0).squeeze(-1); self._dst_fb = self.idx_fb[self._src_fb].long()
-        self._src_tb = torch.nonzero(self.idx_tb >= 0).squeeze(-1); self._dst_tb = self.idx_tb[self._src_tb].long()
+        self.idx_fb, self._src_fb, self._dst_fb = packing.scatter_pairs(idx_fb, self.device)
+        self.idx_tb, self._src_tb, self._dst_tb = packing.scatter_pairs(idx_tb, self.device)
         # the fp16x2 update (csrc/dqn_fused_h2.inc): two-term weight planes (rebuilt by every `dqn_fused_update_h2` call from the masters),
         # the scale table (s | 1 / s | last maxima: 48 floats) and the overflow word
         self.QH, self.QTH, self.QH_tgt = zi(QH_HALVES), zi(QTH_HALVES), zi(QH_HALVES)
@@ -222,18 +166,15 @@ class QNetPacked:
 
     def refresh(self):
         """Rebuild the fragment copies and term planes from the packed masters (after a load / out-of-band change)."""
-        from .policy import split_bf16x3
         with torch.no_grad():
             self.PF[self._dst_f] = self.P[self._src_f]
             self.PT[self._dst_t] = self.P[self._src_t]
             self.PF_tgt[self._dst_f] = self.P_tgt[self._src_f]
-            for dst_buf, master, src, dst in ((self.QB, self.P, self._src_fb, self._dst_fb), (self.QTB, self.P, self._src_tb, self._dst_tb),
-                                              (self.QB_tgt, self.P_tgt, self._src_fb, self._dst_fb)):
-                for term, plane in enumerate(split_bf16x3(master[src])):
-                    dst_buf[dst + 512 * term] = plane
+        packing.write_planes(self.QB, self.P, self._src_fb, self._dst_fb)
+        packing.write_planes(self.QTB, self.P, self._src_tb, self._dst_tb)
+        packing.write_planes(self.QB_tgt, self.P_tgt, self._src_fb, self._dst_fb)
 
     def plane_args(self):
-        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
         return (p(self.QB), p(self.QTB), p(self.QB_tgt), p(self.idx_fb), p(self.idx_tb))
 
 
@@ -345,7 +286,6 @@ class DQN:
         """The gradient of one update through `dqn_fused_update` (csrc/dqn_fused.inc): ALL sampled steps in two persistent launches
         (chain per tile with dW1 / dW3 in registers; dW2 over the saved H1 / dZ2 plane images) + one slab reduction.  bf16x3."""
         pk, lib = self.packed, self._lib
-        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
         S, n = len(chunks), int(chunks[0][0].shape[0])
         tiles = S * n // 32
         if getattr(self, "_fu_rows", 0) < S * n:
@@ -408,7 +348,6 @@ class DQN:
 
     def _fused_launch(self, dev, S, n, aligned, inv_B):
         pk, lib = self.packed, self._lib
-        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
         loss_part = self._fu_loss[:S * n // 32]
         _lib.check(lib.dqn_fused_update(p(pk.P), p(pk.QB), p(pk.QTB), p(pk.P_tgt), p(pk.QB_tgt), p(dev), C.c_int(S), C.c_int64(n),
                                         C.c_float(self.discount), C.c_float(inv_B), p(self._fu_images), p(self._fu_ws), p(pk.G),
@@ -417,7 +356,6 @@ class DQN:
 
     def _fused_launch_h2(self, dev, S, n, aligned, inv_B, flags):
         pk, lib = self.packed, self._lib
-        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
         loss_part = self._fu_loss[:S * n // 32]
         _lib.check(lib.dqn_fused_update_h2(p(pk.P), p(pk.QH), p(pk.QTH), p(pk.P_tgt), p(pk.QH_tgt), p(pk.idx_fb), p(pk.idx_tb),
                                            p(pk.h2_scales), p(pk.h2_overflow), p(dev), C.c_int(S), C.c_int64(n), C.c_float(self.discount),
@@ -435,7 +373,6 @@ class DQN:
         self._updates_issued += 1
         self._h2_guard = False
         pk, lib = self.packed, self._lib
-        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
         st = _lib.stream_ptr()
         B = sum(int(c[0].shape[0]) for c in chunks)
         inv_B = 1.0 / float(B)
@@ -482,7 +419,6 @@ class DQN:
         x = obs.reshape(-1, IN)
         x = x if x.is_contiguous() else x.contiguous()
         out = torch.empty((x.shape[0], NACT), device=self.device)
-        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
         _lib.check(self._lib.dqn_forward(p(self.packed.P), p(self.packed.PF), p(x), C.c_int64(x.shape[0]), p(out),
                                          _lib.stream_ptr()), "dqn_forward")
         return out
@@ -494,7 +430,6 @@ class DQN:
         self._rand.uniform_(generator=self._gen)
         x = obs if obs.is_contiguous() else obs.contiguous()
         out = torch.empty(n, device=obs.device)
-        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
         _lib.check(self._lib.dqn_act(p(self.packed.P), p(self.packed.PF), p(x), C.c_int64(n), p(self._coin), p(self._rand),
                                      C.c_float(epsilon), p(out), None, _lib.stream_ptr()), "dqn_act")
         return out

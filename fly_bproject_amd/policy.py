@@ -3,119 +3,48 @@
 `PackedPolicy` owns ONE flat fp32 buffer in the layout of csrc/mlp_layout.h and re-points the
 `.data` of every `Net` parameter at a strided view into it, so torch (checkpoint I/O, autograd,
 optimizers) and the HIP kernels see the same memory.  Padding and the structural zeros of the
-stacked last layer never receive gradient (`grad_mask`).
+stacked last layer never receive gradient (`grad_mask`).  The format itself -- offsets, sizes, index maps -- is
+packing.py's: this module declares the four layers to it (tests/test_abi_cpu.py holds the result to the header).
 """
 import ctypes as C
 import os
 
 import torch
 
-from . import _lib, options
+from . import _lib, options, packing
+from .packing import split_bf16x3, split_f16x2, untile   # noqa: F401  (read from here by tests and tools)
+
+p = _lib.ptr
 
 IN, IN_PAD, H1, H2, H3, OUT, NACT = 73, 80, 256, 128, 128, 32, 18
-OFF_W1 = 0
-OFF_B1 = OFF_W1 + H1 * IN_PAD
-OFF_W2 = OFF_B1 + H1
-OFF_B2 = OFF_W2 + H2 * H1
-OFF_W3 = OFF_B2 + H2
-OFF_B3 = OFF_W3 + H3 * H2
-OFF_W4 = OFF_B3 + H3
-OFF_B4 = OFF_W4 + OUT * H3
-PACKED = OFF_B4 + OUT                      # 74272
+LAYOUT = packing.Layout([
+    packing.Layer("W1", H1, IN_PAD, "plain", None, "plain"),
+    # layer 2 forward: two K = 128 operands (k < 128, k >= 128), one per half of H1 in LDS
+    packing.Layer("W2", H2, H1, "two_halves", 0, "two_halves"),
+    packing.Layer("W3", H3, H2, "plain", 1, "plain"),
+    # layer 4 forward: split-K over the four waves (the planes keep the generic order)
+    packing.Layer("W4", OUT, H3, "split_k4", 2, "plain")])
+OFF_W1, OFF_W2, OFF_W3, OFF_W4 = LAYOUT.off_w
+OFF_B1, OFF_B2, OFF_B3, OFF_B4 = LAYOUT.off_b
+PACKED = LAYOUT.packed
 ERR_SLOT = OFF_W1 + 76                     # a masked padding element of W1: the "this gradient is invalid" mark (csrc/mlp_grad_w.inc)
-OFF_F1 = 0
-OFF_F2 = OFF_F1 + H1 * IN_PAD
-OFF_F3 = OFF_F2 + H2 * H1
-OFF_F4 = OFF_F3 + H3 * H2
-FRAG = OFF_F4 + OUT * H3                   # 73728
-OFF_TF2 = 0
-OFF_TF3 = OFF_TF2 + H1 * H2
-OFF_TF4 = OFF_TF3 + H2 * H3
-FRAG_T = OFF_TF4 + H3 * OUT                # 53248
-
-
-def _frag_index(n, k, K):
-    """Fragment-order offset of element (n, k) of an operand with K reduced (csrc/mlp_layout.h)."""
-    h, kk = k // (K // 2), k % (K // 2)
-    return (((n // 32) * (K // 8) + kk // 4) * 64 + (h * 32 + n % 32)) * 4 + kk % 4
-
-
-def build_index_maps():
-    """int32 [PACKED] maps master index -> position in PF / PTF (-1: no copy)."""
-    import numpy as np
-    idx_f = np.full(PACKED, -1, np.int32)
-    idx_t = np.full(PACKED, -1, np.int32)
-    layers = [(OFF_W1, H1, IN_PAD, OFF_F1, None), (OFF_W2, H2, H1, OFF_F2, OFF_TF2),
-              (OFF_W3, H3, H2, OFF_F3, OFF_TF3), (OFF_W4, OUT, H3, OFF_F4, OFF_TF4)]
-    for li, (off_w, N, K, off_f, off_t) in enumerate(layers):
-        n, k = np.meshgrid(np.arange(N), np.arange(K), indexing="ij")
-        src = off_w + n * K + k
-        if li == 1:     # layer 2 forward: two K=128 operands (k < 128, k >= 128), one per half of H1 in LDS
-            idx_f[src] = off_f + (k // (K // 2)) * (N * (K // 2)) + _frag_index(n, k % (K // 2), K // 2)
-        elif li < 3:
-            idx_f[src] = off_f + _frag_index(n, k, K)
-        else:       # layer 4 forward: split-K over the four waves
-            w, h, kq, q = k // 32, (k % 32) // 16, (k % 16) // 4, k % 4
-            idx_f[src] = off_f + ((w * 4 + kq) * 64 + (h * 32 + n)) * 4 + q
-        if off_t is not None:   # W^T: K outputs, N reduced
-            idx_t[src] = off_t + _frag_index(k, n, N)
-    for name, idx, size in (("PF", idx_f, FRAG), ("PTF", idx_t, FRAG_T)):
-        used = idx[idx >= 0]
-        assert len(np.unique(used)) == len(used) and used.max() < size, name
-    assert (idx_f >= 0).sum() == FRAG and (idx_t >= 0).sum() == FRAG_T
-    return idx_f, idx_t
-
-
-def _plane_index(n, k, K):
-    """Position (16-bit words) of term 0 of element (n, k) of a bf16x3 operand with K reduced
-    (csrc/mlp_layout.h); terms 1 and 2 follow 512 and 1024 words later."""
-    return (((n // 32) * (K // 16) + k // 16) * 3) * 512 + (((k % 16) // 8) * 32 + n % 32) * 8 + k % 8
-
-
-PB_HALVES, PTB_HALVES = 221184, 159744
-OFF_PB = (0, 61440, 159744, 208896)
-OFF_PTB = (None, 0, 98304, 147456)
-
-
-def build_plane_maps():
-    """int32 [PACKED] maps master index -> term-0 position in PB / PTB (-1: no copy)."""
-    import numpy as np
-    idx_fb = np.full(PACKED, -1, np.int32)
-    idx_tb = np.full(PACKED, -1, np.int32)
-    layers = [(OFF_W1, H1, IN_PAD), (OFF_W2, H2, H1), (OFF_W3, H3, H2), (OFF_W4, OUT, H3)]
-    for li, (off_w, N, K) in enumerate(layers):
-        n, k = np.meshgrid(np.arange(N), np.arange(K), indexing="ij")
-        src = off_w + n * K + k
-        if li == 1:     # two K = 128 operands
-            idx_fb[src] = OFF_PB[li] + (k // 128) * (3 * N * 128) + _plane_index(n, k % 128, 128)
-        else:
-            idx_fb[src] = OFF_PB[li] + _plane_index(n, k, K)
-        if OFF_PTB[li] is not None:     # W^T: K outputs, N reduced
-            idx_tb[src] = OFF_PTB[li] + _plane_index(k, n, N)
-    for idx, size in ((idx_fb, PB_HALVES), (idx_tb, PTB_HALVES)):
-        used = idx[idx >= 0].astype(np.int64)
-        allpos = np.concatenate([used, used + 512, used + 1024])
-        assert len(np.unique(allpos)) == len(allpos) and allpos.max() < size
-    assert 3 * (idx_fb >= 0).sum() == PB_HALVES and 3 * (idx_tb >= 0).sum() == PTB_HALVES
-    return idx_fb, idx_tb
-
+OFF_F1, OFF_F2, OFF_F3, OFF_F4 = LAYOUT.off_f
+FRAG = LAYOUT.frag
+_, OFF_TF2, OFF_TF3, OFF_TF4 = LAYOUT.off_t
+FRAG_T = LAYOUT.frag_t
+PB_HALVES, PTB_HALVES = LAYOUT.pb_halves, LAYOUT.ptb_halves
+OFF_PB, OFF_PTB = LAYOUT.off_pb, LAYOUT.off_ptb
+build_index_maps, build_plane_maps = LAYOUT.index_maps, LAYOUT.plane_maps
 
 # fp16x2 planes of the fused optimizer step (csrc/mlp_fused_h2.inc): PB's / PTB's layout with two terms per k block
-PH_HALVES, PTH_HALVES = PB_HALVES * 2 // 3, PTB_HALVES * 2 // 3
-H2_SCALE_FLOATS, H2_INV, H2_W0 = 2386, 16, 8        # (csrc/mlp_adam.inc: [40, 41] and [64 ..) are mlp_adam_step's rescale bookkeeping)
-H2_SINCE, H2_WMAX, H2_WMAX_SLOTS = 40, 64, 1161
+PH_HALVES, PTH_HALVES = LAYOUT.ph_halves, LAYOUT.pth_halves
+H2_INV, H2_W0 = 16, 8                               # (csrc/mlp_adam.inc: [40, 41] and [64 ..) are mlp_adam_step's rescale bookkeeping)
+H2_SINCE, H2_WMAX, H2_WMAX_SLOTS = 40, 64, (PACKED + 63) // 64
+H2_SCALE_FLOATS = H2_WMAX + 2 * H2_WMAX_SLOTS       # two tables of max |w| per 64 packed elements behind the scales
 H2_CLASSES = ("x", "h1", "h2", "h3", "dz4", "dz3", "dz2", "dz1")
 # where the step steers a class maximum of |scaled value| -- [2^e, 2^(e + 1)) -- and the floor under which a launch is refused
 # (csrc/fs_h2.inc: H2_TARGET_EXP_ACT / _GRAD, H2_CLASS_FLOOR; the tests derive their windows and bars from these)
 H2_TARGET_EXP_ACT, H2_TARGET_EXP_GRAD, H2_CLASS_FLOOR = 7, 2, 2.0 ** -8
-
-
-def split_f16x2(w, scale):
-    """fp32 tensor -> two int16 tensors holding the fp16 terms h0 + h1 ~= w * scale (|error| <= 2^-23 |w scale|)."""
-    y = w * scale
-    h0 = y.to(torch.float16)
-    h1 = (y - h0.float()).to(torch.float16)
-    return [t.view(torch.int16) for t in (h0, h1)]
 
 
 def h2_weight_scale(wmax):
@@ -123,26 +52,6 @@ def h2_weight_scale(wmax):
     import math
     m = min(max(float(wmax), 2.0 ** -4), 2.0 ** 60)
     return 2.0 ** (11 - math.floor(math.log2(m)))
-
-
-def untile(t, n, N):
-    """[rows][N] view of a saved activation / dZ buffer, which the kernels keep in tile-fragment order
-    (csrc/mlp_mfma.hip, frag_off): per 32-row tile and 32-column tile a block of 1024 floats
-    [g][lane][4] with lane = 32 * ((col % 8) // 4) + row % 32, g = (col % 32) // 8."""
-    rows = torch.arange(n, device=t.device).view(-1, 1)
-    cols = torch.arange(N, device=t.device).view(1, -1)
-    c = cols % 32
-    off = ((rows // 32) * (N // 32) + cols // 32) * 1024 + ((c // 8) * 64 + ((c // 4) % 2) * 32 + rows % 32) * 4 + c % 4
-    return t.reshape(-1)[off]
-
-
-def split_bf16x3(w):
-    """fp32 tensor -> three int16 tensors holding the bf16 terms w0 + w1 + w2 == w (exact)."""
-    w0 = w.to(torch.bfloat16)
-    r1 = w - w0.float()
-    w1 = r1.to(torch.bfloat16)
-    w2 = (r1 - w1.float()).to(torch.bfloat16)
-    return [t.view(torch.int16) for t in (w0, w1, w2)]
 
 
 class PackedPolicy:
@@ -179,28 +88,12 @@ class PackedPolicy:
         self.h2_calibration_failures = 0    # data-parallel updates run on bf16x3 because some rank's calibrate_h2 did not settle
         self._h2_reset_scales()
         idx_fb, idx_tb = build_plane_maps()
-        self.idx_fb = torch.from_numpy(idx_fb).to(self.device)
-        self.idx_tb = torch.from_numpy(idx_tb).to(self.device)
-        self._src_fb = torch.nonzero(self.idx_fb >= 0).squeeze(-1)
-        self._dst_fb = self.idx_fb[self._src_fb].long()
-        self._src_tb = torch.nonzero(self.idx_tb >= 0).squeeze(-1)
-        self._dst_tb = self.idx_tb[self._src_tb].long()
+        self.idx_fb, self._src_fb, self._dst_fb = packing.scatter_pairs(idx_fb, self.device)
+        self.idx_tb, self._src_tb, self._dst_tb = packing.scatter_pairs(idx_tb, self.device)
         idx_f, idx_t = build_index_maps()
-        self.idx_f = torch.from_numpy(idx_f).to(self.device)
-        self.idx_t = torch.from_numpy(idx_t).to(self.device)
-        self._src_f = torch.nonzero(self.idx_f >= 0).squeeze(-1)
-        self._dst_f = self.idx_f[self._src_f].long()
-        self._src_t = torch.nonzero(self.idx_t >= 0).squeeze(-1)
-        self._dst_t = self.idx_t[self._src_t].long()
-        P = self.P
-        self.W1 = P[OFF_W1:OFF_B1].view(H1, IN_PAD)
-        self.b1 = P[OFF_B1:OFF_W2]
-        self.W2 = P[OFF_W2:OFF_B2].view(H2, H1)
-        self.b2 = P[OFF_B2:OFF_W3]
-        self.W3 = P[OFF_W3:OFF_B3].view(H3, H2)
-        self.b3 = P[OFF_B3:OFF_W4]
-        self.W4 = P[OFF_W4:OFF_B4].view(OUT, H3)
-        self.b4 = P[OFF_B4:PACKED]
+        self.idx_f, self._src_f, self._dst_f = packing.scatter_pairs(idx_f, self.device)
+        self.idx_t, self._src_t, self._dst_t = packing.scatter_pairs(idx_t, self.device)
+        (self.W1, self.b1), (self.W2, self.b2), (self.W3, self.b3), (self.W4, self.b4) = LAYOUT.matrices(self.P)
         self.views = {
             "shared_net.0.weight": self.W1[:, :IN], "shared_net.0.bias": self.b1,
             "shared_net.2.weight": self.W2, "shared_net.2.bias": self.b2,
@@ -209,19 +102,9 @@ class PackedPolicy:
             "to_mean.2.weight": self.W4[:NACT, :64], "to_mean.2.bias": self.b4[:NACT],
             "to_value.2.weight": self.W4[NACT:NACT + 1, 64:], "to_value.2.bias": self.b4[NACT:NACT + 1],
         }
-        params = dict(net.named_parameters())
-        assert set(params) == set(self.views), "Net does not have the reference's parameter set"
-        with torch.no_grad():
-            for k, view in self.views.items():
-                view.copy_(params[k].data.to(self.device))
-                params[k].data = view                       # one copy of truth
-        mask = torch.zeros(PACKED, dtype=torch.float32, device=self.device)
-        for k, view in self.views.items():
-            off = view.storage_offset()
-            idx = torch.arange(PACKED, device=self.device).as_strided(view.shape, view.stride(), off)
-            mask[idx.reshape(-1)] = 1.0
-        self.grad_mask = mask
-        assert int(mask.sum().item()) == 69587            # every reference parameter exactly once
+        packing.bind_parameters(net, self.views)
+        self.grad_mask = packing.grad_mask(self.views, PACKED, self.device)
+        assert int(self.grad_mask.sum().item()) == 69587            # every reference parameter exactly once
         self.refresh()
 
     def refresh(self):
@@ -238,11 +121,8 @@ class PackedPolicy:
     refresh_transposes = refresh
 
     def _refresh_planes(self):
-        with torch.no_grad():
-            for dst_buf, src, dst in ((self.PB, self._src_fb, self._dst_fb), (self.PTB, self._src_tb, self._dst_tb)):
-                for term, plane in enumerate(split_bf16x3(self.P[src])):
-                    dst_buf[dst + 512 * term] = plane
-
+        packing.write_planes(self.PB, self.P, self._src_fb, self._dst_fb)
+        packing.write_planes(self.PTB, self.P, self._src_tb, self._dst_tb)
         if self.h2_live():
             self._refresh_planes_h2()
 
@@ -266,7 +146,6 @@ class PackedPolicy:
         safe (mlp_adam_step rescales by itself; this launch also seeds its bookkeeping in the table)."""
         if self.device.type != "cuda":
             return                                  # (layout-only uses of the class on the CPU: tests/test_dist_cpu.py)
-        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
         _lib.check(self._lib.mlp_h2_rescale(p(self.P), p(self.idx_fb), p(self.idx_tb), p(self.PH), p(self.PTH), p(self.h2_scales),
                                             _lib.stream_ptr()), "mlp_h2_rescale")
 
@@ -312,13 +191,11 @@ class PackedPolicy:
     def _plane_args(self):
         if not self._planes_live():
             return (None, None, None, None)
-        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
         return (p(self.PB), p(self.PTB), p(self.idx_fb), p(self.idx_tb))
 
     def _h2_args(self):
         if not self.h2_live():
             return (None, None, None, C.c_int(0))
-        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
         # a RESCALE step (the kernel re-derives the weight scales from the weights before it splits under them) every `period` APPLIED
         # steps -- the kernel counts them on the device, a refused step does not count --, often enough that a weight cannot have
         # drifted out of the scale's 16x headroom: an Adam step moves it by at most 3.2 lr
@@ -347,7 +224,7 @@ class PackedPolicy:
         mu = torch.empty((n, NACT), device=self.device) if want_mu else None
         v = torch.empty((n,), device=self.device) if want_v else None
         s = saves or {}
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+        ptr = lambda t: None if t is None else p(t)   # noqa: E731
         _lib.check(self._lib.mlp_forward(ptr(self.P), ptr(self.PF), ptr(x2), C.c_int64(n), ptr(mu), ptr(v), ptr(s.get("out")),
                                          ptr(s.get("h1")), ptr(s.get("h2")), ptr(s.get("h3")),
                                          self.pb_ptr() if saves else self.infer_pb_ptr(), _lib.stream_ptr()),
@@ -436,7 +313,6 @@ class PackedPolicy:
         for t in (old_logp, adv, target):
             assert t.is_contiguous() and t.numel() == n
         s, d = self.saves, self.dz
-        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
         st = _lib.stream_ptr()
         inv_b = 1.0 / float(global_rows if global_rows else n)
         if self.fused_step and self.gemm == "bf16x3":
@@ -472,7 +348,6 @@ class PackedPolicy:
         """`mlp_fused_grad`: one persistent launch + the slab reduction.  dump=True (tests) also writes the chain's values into
         self.saves / self.dz exactly as the three-launch path leaves them."""
         n = x.shape[0]
-        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
         if self._fused_ws is None:
             self._fused_ws = torch.empty(int(max(self._lib.mlp_fused_workspace_floats(), self._lib.mlp_fused_h2_workspace_floats())),
                                          device=self.device)
@@ -571,7 +446,6 @@ class PackedPolicy:
         (data-parallel ranks: G comes out of the all-reduce); the step counter then ping-pongs between two
         device words so that no workgroup reads a value another one has already advanced.  grad_invalid: optional int32 device
         word (the err word of the peer-to-peer exchange); nonzero = the launch refuses the step (fail closed)."""
-        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
         self.version += 1
         self.steps_issued += 1
         step_in = self.step

@@ -33,9 +33,7 @@ from .fly import Fly
 from .params import NUM_DOF
 
 
-def p(x):
-    """The device address of a tensor, as the C ABI takes it."""
-    return C.c_void_p(x.data_ptr())
+p = _lib.ptr
 
 
 class Net(nn.Module):

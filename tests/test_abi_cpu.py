@@ -73,6 +73,67 @@ def test_fly_fails_loudly_without_gpu():
             Fly(args)
 
 
+def _layout_macros():
+    """Every offset / size macro of the two layout headers and every *_ABI size of flyhip.h, by name."""
+    names = []
+    for path, pattern in (("fly_bproject_amd/csrc/mlp_layout.h", r"^#define\s+(MLP_\w+)[ \t]+\S"),
+                          ("fly_bproject_amd/csrc/dqn_layout.h", r"^#define\s+(DQN_\w+)[ \t]+\S"),
+                          ("include/flyhip.h", r"^#define\s+((?:MLP|DQN)_\w+_ABI)[ \t]+\S")):
+        found = re.findall(pattern, open(os.path.join(REPO, path)).read(), flags=re.M)
+        assert len(found) >= 15, path
+        names += found
+    return names
+
+
+def _python_layout_values():
+    """The same names as fly_bproject_amd/packing.py derives them for the two declared networks."""
+    from fly_bproject_amd import dqn as D, policy as P
+    want = {}
+    for pre, M, dims in (("MLP", P, ("IN", "IN_PAD", "H1", "H2", "H3", "OUT", "NACT")), ("DQN", D, ("IN", "IN_PAD", "H", "OUT", "NACT"))):
+        L = M.LAYOUT
+        want.update({"%s_%s" % (pre, d): getattr(M, d) for d in dims})
+        for i, (w, b, f) in enumerate(zip(L.off_w, L.off_b, L.off_f), 1):
+            want.update({"%s_OFF_W%d" % (pre, i): w, "%s_OFF_B%d" % (pre, i): b, "%s_OFF_F%d" % (pre, i): f})
+        want.update({pre + "_PACKED_FLOATS": L.packed, pre + "_FRAG_FLOATS": L.frag, pre + "_FRAG_T_FLOATS": L.frag_t})
+        t, b, tb = ("TF", "PB", "PTB") if pre == "MLP" else ("T", "QB", "QTB")
+        for i, (ot, opb, optb) in enumerate(zip(L.off_t, L.off_pb, L.off_ptb), 1):
+            want["%s_OFF_%s%d" % (pre, b, i)] = opb
+            if ot is not None:
+                want.update({"%s_OFF_%s%d" % (pre, t, i): ot, "%s_OFF_%s%d" % (pre, tb, i): optb})
+        want.update({"%s_%s_HALVES" % (pre, b): L.pb_halves, "%s_%s_HALVES" % (pre, tb): L.ptb_halves})
+        th, tth = ("PH", "PTH") if pre == "MLP" else ("QH", "QTH")
+        want.update({"%s_%s_HALVES_ABI" % (pre, b): L.pb_halves, "%s_%s_HALVES_ABI" % (pre, tb): L.ptb_halves,
+                     "%s_%s_HALVES_ABI" % (pre, th): L.ph_halves, "%s_%s_HALVES_ABI" % (pre, tth): L.pth_halves,
+                     pre + "_PACKED_FLOATS_ABI": L.packed, pre + "_FRAG_FLOATS_ABI": L.frag, pre + "_FRAG_T_FLOATS_ABI": L.frag_t})
+    want["MLP_H2_SCALE_FLOATS_ABI"] = P.H2_SCALE_FLOATS
+    # the layers themselves are the headers' matrices
+    assert [(l.N, l.K) for l in P.LAYOUT.layers] == [(P.H1, P.IN_PAD), (P.H2, P.H1), (P.H3, P.H2), (P.OUT, P.H3)]
+    assert [(l.N, l.K) for l in D.LAYOUT.layers] == [(D.H, D.IN_PAD), (D.H, D.H), (D.OUT, D.H)]
+    return want
+
+
+def test_python_layout_matches_the_headers(tmp_path):
+    """The numbers fly_bproject_amd/packing.py derives equal the macros of csrc/mlp_layout.h, csrc/dqn_layout.h and the *_ABI
+    sizes of include/flyhip.h, as a host C++ program that includes the three prints them.  No compiler is a failure."""
+    import shutil
+    import subprocess
+    names = _layout_macros()
+    src = tmp_path / "layout_macros.cpp"
+    src.write_text('#include <cstdio>\n#include "flyhip.h"\n#include "mlp_layout.h"\n#include "dqn_layout.h"\nint main() {\n'
+                   + "".join('    std::printf("%s %%ld\\n", (long)(%s));\n' % (n, n) for n in names) + "    return 0;\n}\n")
+    cxx = shutil.which("g++")
+    cmd = [cxx] if cxx else [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-x", "c++"]
+    exe = str(tmp_path / "layout_macros")
+    subprocess.check_call(cmd + ["-std=c++17", "-I", os.path.join(REPO, "include"), "-I", os.path.join(REPO, "fly_bproject_amd", "csrc"),
+                                 str(src), "-o", exe])
+    lines = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split("\n")
+    got = {n: int(v) for n, v in (line.split() for line in lines if line)}
+    assert set(got) == set(names) and len(got) == len(names)
+    want = _python_layout_values()
+    assert set(got) == set(want), sorted(set(got) ^ set(want))
+    assert got == want, {n: (got[n], want[n]) for n in got if got[n] != want[n]}
+
+
 def test_bf16x3_planes_and_tile_layout_maps():
     """Host-side layout logic of the bf16x3 path and of the tile-fragment saved tensors: the plane
     index maps are injective and cover the buffers exactly, the three-term split is exact, and
