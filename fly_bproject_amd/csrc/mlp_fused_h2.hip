@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include "flyhip.h"
 #include "mlp_layout.h"
+#include "h2_warm.h"
 #include "obs_norm.h"
 #include "launch.h"
 

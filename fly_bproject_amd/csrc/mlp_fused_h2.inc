@@ -326,24 +326,32 @@ __global__ __launch_bounds__(THREADS, 1) void mlp_fused_step_h2_kernel(
 
     long tile = blockIdx.x;
     if (tile < ntiles) x_fetch((int)tile, tid);
-    if (tid < 32) {     // loss-phase constants per output column (ppo.py:185-189) and the scale table
-        const bool act = tid < MLP_NACT;
-        const float L = act ? sqrtf(var[tid]) : 1.0f;
-        c_invL[tid] = act ? 1.0f / L : 0.0f;
-        c_invVar[tid] = act ? 1.0f / var[tid] : 0.0f;
-        float hld = act ? logf(L) : 0.0f;
-#pragma unroll
-        for (int o = 1; o < 32; o <<= 1) hld += __shfl_xor(hld, o, 32);
-        if (tid == 0) c_hld[0] = hld;
-        sc[tid] = fsc[tid];
+    // THE HEAD: everything else the kernel reads before its first tile is requested HERE, behind the first x DMA and ahead of the one
+    // wait below -- one round trip to memory instead of five in a row (var, the scale table, three groups of biases, each loaded,
+    // waited for and stored before the next was requested) with layer 1's first weight fragments a sixth one behind the barriers.
+    // No load stands under a condition (the compiler sinks such a load below its branch, behind the wait): a thread without a
+    // column of its own reads a word of somebody else's.  The arithmetic on the loaded values is what it was.
+    WeightHead2 w1;                                                       // the FIRST tile's layer-1 head; later tiles: the loop top
+    h2_gemm_prefetch<MLP_IN_PAD>(w1, PH + H2_OFF_PH1, 2 * wave, tid & 63);
+    float g_var = var[tid < MLP_NACT ? tid : 0], g_sc = fsc[tid & 31];
+    float g_b1 = P[MLP_OFF_B1 + tid], g_b23 = P[tid < MLP_H2 ? MLP_OFF_B2 + tid : MLP_OFF_B3 + (tid - MLP_H2)];
+    float g_b4 = P[MLP_OFF_B4 + (tid & (MLP_OUT - 1))];
+    const float s_h1 = fsc[H2C_H1], s_h2 = fsc[H2C_H2], s_h3 = fsc[H2C_H3];      // (uniform: scalar loads)
+    // L2 warm-up (h2_warm.h): one dword of every 128-byte line of this workgroup's share of the two weight planes, into registers
+    // nobody reads.  asm, so that the compiler keeps them; the registers stay reserved up to the wait below, which is the only
+    // wait these loads ever stand in front of.
+    float warm0, warm1;
+    {
+        constexpr unsigned PHB = H2_PH_HALVES * 2, PTHB = H2_PTH_HALVES * 2;
+        static_assert(h2_warm_loads(PHB, THREADS) == 1 && h2_warm_loads(PTHB, THREADS) == 1, "one load per plane and thread");
+        const unsigned sh = h2_warm_share(blockIdx.x);
+        const unsigned o0 = h2_warm_offset(PHB, sh, 0, (unsigned)tid, THREADS), o1 = h2_warm_offset(PTHB, sh, 0, (unsigned)tid, THREADS);
+        asm volatile("global_load_dword %0, %2, %4\n\tglobal_load_dword %1, %3, %5"
+                     : "=&v"(warm0), "=&v"(warm1) : "v"(o0), "v"(o1), "s"(PH), "s"(PTH) : "memory");
     }
-    bias1[tid] = P[MLP_OFF_B1 + tid] * fsc[H2C_H1];                      // (the epilogues add the bias times s)
-    if (tid < MLP_H2) bias2[tid] = P[MLP_OFF_B2 + tid] * fsc[H2C_H2];
-    else bias3[tid - MLP_H2] = P[MLP_OFF_B3 + tid - MLP_H2] * fsc[H2C_H3];
-    if (tid < MLP_OUT) bias4[tid] = P[MLP_OFF_B4 + tid];
 #pragma unroll
     for (int c = 0; c < H2_NACT_CLASSES; ++c) amax[c * THREADS + tid] = 0.0f;
-    if (!STAMP) {       // the accumulator clears HERE, while the first rows and the biases are in flight (mlp_fused_step.inc)
+    if (!STAMP) {       // the accumulator clears HERE, while everything above is in flight (mlp_fused_step.inc)
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -356,7 +364,23 @@ __global__ __launch_bounds__(THREADS, 1) void mlp_fused_step_h2_kernel(
         for (int b = 0; b < 2; ++b) { asm volatile("" : "+a"(aW3[1][b])); asm volatile("" : "+v"(aW3[0][b])); }
         asm volatile("" : "+v"(aW4));
     }
-    fs_dma_drain();
+    // the one wait of the head (fs_dma_drain's, taking the loaded values so that their loads stand in front of it)
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(g_var), "+v"(g_sc), "+v"(g_b1), "+v"(g_b23), "+v"(g_b4), "+v"(warm0), "+v"(warm1) : : "memory");
+    if (tid < 32) {     // loss-phase constants per output column (ppo.py:185-189) and the scale table
+        const bool act = tid < MLP_NACT;
+        const float L = act ? sqrtf(g_var) : 1.0f;
+        c_invL[tid] = act ? 1.0f / L : 0.0f;
+        c_invVar[tid] = act ? 1.0f / g_var : 0.0f;
+        float hld = act ? logf(L) : 0.0f;
+#pragma unroll
+        for (int o = 1; o < 32; o <<= 1) hld += __shfl_xor(hld, o, 32);
+        if (tid == 0) c_hld[0] = hld;
+        sc[tid] = g_sc;
+    }
+    bias1[tid] = g_b1 * s_h1;                                             // (the epilogues add the bias times s)
+    if (tid < MLP_H2) bias2[tid] = g_b23 * s_h2;
+    else bias3[tid - MLP_H2] = g_b23 * s_h3;
+    if (tid < MLP_OUT) bias4[tid] = g_b4;
     __syncthreads();                                                      // the scale table is in LDS
     if (tile < ntiles) {                                                  // the workgroup's first tile: converted at once
         H2XStoreOps xc0(xs, X, tid, sc[H2C_X]);
@@ -385,8 +409,8 @@ __global__ __launch_bounds__(THREADS, 1) void mlp_fused_step_h2_kernel(
         if (STAMP) { stamps = reinterpret_cast<unsigned long long*>(dump.out) + ((long)blockIdx.x * 64 + tslot) * FS_STAMP_SLOTS; ++tslot; }
         stamp<STAMP>(stamps, 0);
         if (!STAMP) fs_split(n);
-        WeightHead2 w1;
-        h2_gemm_prefetch<MLP_IN_PAD>(w1, PH + H2_OFF_PH1, 2 * wave, lane);
+        // (the workgroup's first tile: requested at kernel entry.  A wave-uniform compare of 32-bit tile numbers; the loop body exists once)
+        if ((int)tile != (int)blockIdx.x) h2_gemm_prefetch<MLP_IN_PAD>(w1, PH + H2_OFF_PH1, 2 * wave, lane);
         stamp<STAMP>(stamps, 1);
         if (!STAMP) fs_split(n);
 
@@ -723,6 +747,16 @@ __global__ __launch_bounds__(THREADS, 1) void mlp_fused_step_h2_kernel(
         __syncthreads();
         stamp<STAMP>(stamps, 11);
         if (!STAMP) fs_split(n);
+        // w1 is dead from P1 on.  The (empty) definition says so: without it the loop-top condition, which liveness does not see
+        // through, would keep w1's 16 registers reserved through every tile for a value that only the first tile reads.
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                fs_u32x4 nothing;
+                asm volatile("" : "=v"(nothing));
+                w1.b[s].p[p] = __builtin_bit_cast(float4, nothing);
+            }
     }
     if (STAMP) stamps = reinterpret_cast<unsigned long long*>(dump.out) + ((long)blockIdx.x * 64 + 63) * FS_STAMP_SLOTS;
     stamp<STAMP>(stamps, 0);
@@ -730,7 +764,9 @@ __global__ __launch_bounds__(THREADS, 1) void mlp_fused_step_h2_kernel(
 
     // ---- one partial slab per workgroup (the packed gradient's layout); the products leave WITH their scale factors, which workgroup
     //      0 leaves for the reduction behind the class maxima: [G * 8 + l] = 1 / (s_z s_a) of layer l + 1's dW, [G * 8 + 4 + l] = 1 / s_z (db)
-    const int lane = tid & 63;
+    int tid_tail = tid;       // (made again from a value of its own: the lane number of the head is not kept in a register -- or spilled --
+    asm volatile("" : "+v"(tid_tail));                                    //  across the tile loop for the tail)
+    const int lane = tid_tail & 63;
     const unsigned G = gridDim.x, wg = blockIdx.x;
     if (wg == 0 && tid < 4) {
         const float iz = sc[H2_FSC_INV + H2C_Z1 - tid];                       // layer tid + 1: dz1 is class 7, dz4 class 4

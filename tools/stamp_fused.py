@@ -62,6 +62,18 @@ tot = d.sum(1).mean()
 print("tiles stamped: %d   cycles per tile (wave 0): mean %.0f  min %d  max %d" % (len(d), tot, d.sum(1).min(), d.sum(1).max()))
 for i, nm in enumerate(names):
     print("  %-26s %8.0f cycles  %5.1f %%" % (nm, d[:, i].mean(), 100 * d[:, i].mean() / tot))
+# by tile index: a workgroup's 1st, 2nd, ... tile (what a launch pays because it starts cold shows as the 1st against the others)
+short = ["P0", "P1", "P1 bar", "P2", "P3", "P4", "P5", "P6", "P7", "P8", "P8 bar"]
+print("by tile index (mean cycles over the workgroups that ran such a tile):")
+print("  %-6s %5s %8s" % ("tile", "wgs", "total") + "".join(" %7s" % nm for nm in short))
+for t in range(per):
+    dt = np.array([np.diff(s[b, t, :12]) for b in range(grid) if s[b, t, 11] > 0])
+    if len(dt):
+        print("  %-6s %5d %8.0f" % ("%d." % (t + 1), len(dt), dt.sum(1).mean()) + "".join(" %7.0f" % v for v in dt.mean(0)))
+ran = s[:, 0, 11] > 0
+print("kernel entry -> first tile: loop entry %.0f | stamp 1 (layer 1's first weight fragments requested, its GEMM starts) %.0f | "
+      "stamp 2 (P1 done) %.0f   (the wait for those fragments, in front of the first MFMA, is inside P1: the 1st tile's P1 against the others')"
+      % ((s[ran, 62, 2] - s[ran, 62, 0]).mean(), (s[ran, 0, 1] - s[ran, 62, 0]).mean(), (s[ran, 0, 2] - s[ran, 62, 0]).mean()))
 gaps = np.array([s[b, t + 1, 0] - s[b, t, 11] for b in range(grid) for t in range(per - 1) if s[b, t + 1, 11] > 0])
 print("between tiles (stamp 11 of tile i -> stamp 0 of tile i+1): mean %.0f cycles" % gaps.mean())
 print("loop entry -> first tile's stamp 0: mean %.0f; last tile's stamp 11 -> loop exit: mean %.0f" %
