@@ -62,6 +62,7 @@ SYMBOLS = {
     "ppo_td_gae_vnorm": [_P, _P, _P, _P, _P, _F, _F, _L, _L, _P, _P, _P, _I, _P],
     "ppo_value_norm_merge": [_P, _P, _L, _P, _P, _P],
     "ppo_value_norm_apply": [_P, _L, _P, _P, _P],
+    "ppo_lambda_targets": [_P, _P, _P, _L, _P, _P, _P],
     "ppo_td_gae_episodic": [_P, _P, _P, _P, _P, _P, _L, _F, _F, _L, _L, _P, _P, _I, _P],
     "ppo_td_gae_episodic_vnorm": [_P, _P, _P, _P, _P, _P, _L, _P, _F, _F, _L, _L, _P, _P, _P, _I, _P],
     "ppo_minibatch_gather": [_P] * 5 + [_L, C.c_uint32, C.c_uint32, _L, _L] + [_P] * 6 + [_P],

@@ -292,6 +292,23 @@ int ppo_value_norm_apply(const float* target, int64_t n, const float* table, flo
     return FLY_OK;
 }
 
+int ppo_lambda_targets(const float* adv, const float* v, const float* table, int64_t n, float* target_out, double* sets,
+                       void* stream)
+{
+    if (!adv || !v || !target_out) return fail(FLY_E_ARG, "ppo_lambda_targets: null pointer");
+    if (n < 0) return fail(FLY_E_ARG, "ppo_lambda_targets: n must be >= 0");
+    if ((reinterpret_cast<uintptr_t>(adv) | reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(table) |
+         reinterpret_cast<uintptr_t>(target_out)) & 3)
+        return fail(FLY_E_ARG, "ppo_lambda_targets: a float32 buffer is not 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(sets) & 7) return fail(FLY_E_ARG, "ppo_lambda_targets: sets is not 8-byte aligned");
+    if ((target_out < adv + n && adv < target_out + n) || (target_out < v + n && v < target_out + n))
+        return fail(FLY_E_ARG, "ppo_lambda_targets: target_out must not alias the inputs");
+    if (n == 0 && !sets) return FLY_OK;                     // nothing to write at all
+    hipError_t e = flyhip_launch_lambda_targets(adv, v, table, n, target_out, sets, stream);
+    if (e != hipSuccess) return hip_fail(e, "ppo_lambda_targets launch");
+    return FLY_OK;
+}
+
 // the checks the two episodic entry points share; `what` names the caller in the message
 static int check_episodic(const char* what, bool any_null, int64_t max_episode_length, int64_t T, int64_t N, int mode_flags)
 {

@@ -51,6 +51,10 @@ hipError_t flyhip_launch_value_norm_merge(const double* stats_in, const double* 
                                           float* table_out, void* stream);
 hipError_t flyhip_launch_value_norm_apply(const float* target, int64_t n, const float* table, float* out, void* stream);
 
+// value_target.hip
+hipError_t flyhip_launch_lambda_targets(const float* adv, const float* v, const float* table, int64_t n, float* target_out,
+                                        double* sets, void* stream);
+
 // gae_episodic.hip
 hipError_t flyhip_launch_td_gae_episodic(const float* reward, const float* v, const float* v_next, const int64_t* reset,
                                          const int64_t* progress, const int64_t* ended_prev, int64_t max_episode_length,

@@ -38,7 +38,7 @@ OPTIONS = (
     Option("minibatch", "reference", ("reference", "shuffled")), Option("minibatch_seed", None),
     Option("action_noise", "white", ("white", "ar1")), Option("noise_rho", 0.5),
     Option("normalize_obs", False), Option("obs_clip", 5.0), Option("normalize_value", False),
-    Option("normalize_advantage", False),
+    Option("normalize_advantage", False), Option("lambda_returns", False),
     Option("graph", False), Option("reuse_rollout_values", True), Option("log_throughput", False),
     Option("persistent_rollout", True, env="FLY_PERSISTENT_ROLLOUT"), Option("async_log", True, env="FLY_ASYNC_LOG"),
     Option("update_backend", "hip"), Option("dp_mode", "grad_allreduce", ("grad_allreduce", "param_average")),
@@ -146,6 +146,7 @@ class Options(EnvOptions):
     obs_clip: float
     normalize_value: bool
     normalize_advantage: bool
+    lambda_returns: bool
     graph: bool
     reuse_rollout_values: bool
     log_throughput: bool
@@ -214,6 +215,7 @@ def resolve(args, environ):
         minibatch=minibatch, minibatch_seed=(int(seed if mb_seed is None else mb_seed) + env["rank"] * RANK_SEED_STRIDE) & 0xFFFFFFFF,
         action_noise=action_noise, noise_rho=noise_rho, normalize_obs=normalize_obs, obs_clip=obs_clip,
         normalize_value=bool(_get(args, "normalize_value")), normalize_advantage=bool(_get(args, "normalize_advantage")),
+        lambda_returns=bool(_get(args, "lambda_returns")),
         graph=graph, reuse_rollout_values=bool(_get(args, "reuse_rollout_values")), log_throughput=bool(_get(args, "log_throughput")),
         async_log=bool(_wanted(args, environ, "async_log")), update_backend=_get(args, "update_backend"), dp_mode=dp_mode,
         dp_allreduce=dp_allreduce, gemm=gemm, step_gemm=step_gemm, mini_chunk_size=mini_chunk_size, rollout_size=rollout_size,
@@ -221,9 +223,9 @@ def resolve(args, environ):
 
 
 def projection(o):
-    """The record's statement of what a training state depends on (train_state.META_FIELDS).  An option that is off stores
-    None for its dependent values (`noise_rho` without ar1, `obs_clip` without normalize_obs, the seeds and ranges of features
-    that are off): they mean nothing then, and must not block a resume."""
+    """The record's statement of what a training state depends on (train_state.META_FIELDS and META_EXT_FIELDS).  An option
+    that is off stores None for its dependent values (`noise_rho` without ar1, `obs_clip` without normalize_obs, the seeds and
+    ranges of features that are off): they mean nothing then, and must not block a resume."""
     return {
         "num_envs": o.num_envs, "rollout_size": o.rollout_size, "variant": o.variant, "reward": o.reward,
         "world_size": o.world_size, "rank": o.rank, "gae": o.gae, "minibatch": o.minibatch,
@@ -233,5 +235,5 @@ def projection(o):
         "normalize_value": o.normalize_value, "normalize_advantage": o.normalize_advantage, "randomize": o.randomize,
         "dr_ranges": [[float(lo), float(hi)] for lo, hi in o.dr_ranges] if o.randomize else None,
         "dr_seed": o.dr_seed if o.randomize else None, "gemm": o.gemm, "step_gemm": o.step_gemm,
-        "persistent_rollout": o.persistent_rollout, "dp_mode": o.dp_mode,
+        "persistent_rollout": o.persistent_rollout, "dp_mode": o.dp_mode, "lambda_returns": o.lambda_returns,
     }

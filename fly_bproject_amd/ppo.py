@@ -150,6 +150,7 @@ class PPO:
         if opts.resume:
             self._resume_state = train_state.read_state_file(self.training_state_path(opts.resume_path, opts.rank))
             train_state.check_meta(self._resume_state.get("meta"), args)
+            train_state.check_meta_ext(self._resume_state.get("meta_ext"), args)
         self.env = env if env is not None else Fly(args)           # ppo.py:110
         self.num_acts = self.env.num_act
         self.num_obs = self.env.num_obs
@@ -195,6 +196,10 @@ class PPO:
         # opt-in (`normalize_value`, rl_games' normalize_value): the critic regresses on TD targets kept at zero mean / unit
         # variance by running statistics, and make_data maps its outputs back to reward units
         self.normalize_value = opts.normalize_value
+        # opt-in (`lambda_returns`, rl_games' / SB3's `returns`): the critic regresses on the lambda-return A_t + V(s_t) of the
+        # estimator in use, made by one launch behind the unchanged GAE kernel.  NOT the reference's critic
+        # target (the one-step TD target, ppo.py:160).
+        self.lambda_returns = opts.lambda_returns
         # opt-in (`gae="episodic"`): per-step end flags, a recurrence that stops at episode ends, a bootstrap through time-outs
         # and no training signal from the step that performs a reset.  NOT the reference's estimator (Q1/Q2).
         # (self.gae, above)
@@ -415,8 +420,9 @@ class PPO:
         """make_data's GAE pass with value normalisation: raw targets and advantages under the COMMITTED table plus the targets'
         moments (ppo_td_gae_vnorm; with gae='episodic' ppo_td_gae_episodic_vnorm, which reads the flag rows, not `done_f`), S_v
         with them folded in and its table into the scratch pair (ppo_value_norm_merge; all ranks' sets in rank order), and the
-        targets normalised under the scratch table (ppo_value_norm_apply).  Nothing committed is written, so it is idempotent
-        on a finished rollout."""
+        targets normalised under the scratch table (ppo_value_norm_apply).  With `lambda_returns` the targets and their moments
+        are overwritten by the lambda-returns' right behind the GAE kernel, so everything after it is theirs.  Nothing committed
+        is written, so it is idempotent on a finished rollout."""
         T, n = self.rollout_size, int(self.args.num_envs)
         if self.gae == "episodic":
             _lib.check(self._lib.ppo_td_gae_episodic_vnorm(
@@ -429,12 +435,24 @@ class PPO:
                 p(self.all_reward), p(values[:T]), p(values[1:]), p(done_f), p(self._value_table), C.c_float(self.gamma),
                 C.c_float(self.lmbda), C.c_int64(T), C.c_int64(n), p(self._target), p(self.all_advantage), p(self._value_sets),
                 C.c_int(mode), _lib.stream_ptr()), "ppo_td_gae_vnorm")
+        if self.lambda_returns:
+            self._lambda_targets(values, self._value_table, self._value_sets)      # the targets AND their moments: S_v is theirs
         sets = self._all_rank_sets(self._value_sets, "_keep_value_sets")
         _lib.check(self._lib.ppo_value_norm_merge(p(self._value_stats), p(sets), C.c_int64(sets.shape[0]),
                                                   p(self._value_stats_next), p(self._value_table_next), _lib.stream_ptr()),
                    "ppo_value_norm_merge")
         _lib.check(self._lib.ppo_value_norm_apply(p(self._target), C.c_int64(T * n), p(self._value_table_next),
                                                   p(self._target_norm), _lib.stream_ptr()), "ppo_value_norm_apply")
+
+    def _lambda_targets(self, values, table, sets):
+        """Opt-in (`lambda_returns`): _target <- all_advantage + v(obs_t) in reward units (ppo_lambda_targets: one launch, no
+        host sync), from the advantages the GAE kernel has just written -- raw, so before _normalize_advantage -- and the critic
+        outputs it read.  `table` / `sets` (value normalisation) or None: denormalise v under the committed table, and write
+        the float64 moment sets of the new targets over the TD targets'."""
+        T, n = self.rollout_size, int(self.args.num_envs)
+        _lib.check(self._lib.ppo_lambda_targets(
+            p(self.all_advantage), p(values[:T]), p(table) if table is not None else None, C.c_int64(T * n), p(self._target),
+            p(sets) if sets is not None else None, _lib.stream_ptr()), "ppo_lambda_targets")
 
     def _commit_value_stats(self):
         """S_v <- scratch, table <- scratch table: the next make_data denormalises under the table this update trained on."""
@@ -563,7 +581,8 @@ class PPO:
     def make_data(self):
         """ppo.py:157-171: TD target and GAE.  `all_done` is the [N,1] mask of the LAST step,
         broadcast over T (Q1), and the recurrence never resets at episode ends (Q2).  With gae='episodic' the estimator of
-        DESIGN.md 3.3d instead, from the per-step flag rows."""
+        DESIGN.md 3.3d instead, from the per-step flag rows.  With lambda_returns the critic's target is the advantage plus
+        v(obs_t) instead of the TD target; the advantages are the same either way."""
         T, n = self.rollout_size, self.args.num_envs
         with torch.no_grad():
             ring = self._obs_ring
@@ -596,6 +615,8 @@ class PPO:
                         C.c_float(self.lmbda), C.c_int64(T), C.c_int64(n), p(self._target), p(self.all_advantage),
                         C.c_int(mode), _lib.stream_ptr()), "ppo_td_gae")
                 self._keep = (values, done_f)                       # alive until the stream has consumed them
+            if self.lambda_returns and not self.normalize_value:
+                self._lambda_targets(values, None, None)            # (with normalize_value: inside _td_gae_vnorm)
             if self.normalize_advantage:
                 self._normalize_advantage()
         obs = self._obs_norm_ring[:T] if self.normalize_obs else self.all_obs
@@ -1227,7 +1248,8 @@ class PPO:
         if self.normalize_value:
             for k in ("value_stats", "value_table", "value_stats_next", "value_table_next"):
                 agent[k] = pack(getattr(self, "_" + k))
-        state = {"format": train_state.FORMAT, "meta": self._training_state_meta(), "policy": self.policy.training_state(),
+        state = {"format": train_state.FORMAT, "meta": self._training_state_meta(),
+                 "meta_ext": train_state.expected_meta_ext(self.args), "policy": self.policy.training_state(),
                  "agent": agent, "env": self.env.training_state()}
         tmp = path + ".tmp"
         torch.save(state, tmp)
@@ -1253,6 +1275,7 @@ class PPO:
         if self.update_backend != "hip":
             raise ValueError("load_training_state: update_backend=%r is not part of a training state" % (self.update_backend,))
         train_state.compare_meta(state.get("meta"), self._training_state_meta())
+        train_state.check_meta_ext(state.get("meta_ext"), self.args)
         agent = train_state.block(state, "agent")
         restore, value = train_state.restore, train_state.value
         for mine, key, on in ((getattr(self, "_obs_stats", None), "obs_stats", self.normalize_obs),

@@ -4,11 +4,13 @@
 A state file is ONE dict written by torch.save with every tensor on the CPU -- tensors, numbers, strings, lists and dicts only,
 so it loads with `torch.load(..., weights_only=True)`:
 
-    {"format": 1, "meta": {...}, "policy": {...}, "agent": {...}, "env": {...}}
+    {"format": 1, "meta": {...}, "meta_ext": {...}, "policy": {...}, "agent": {...}, "env": {...}}
 
 `meta` names everything the MEANING of the three state blocks depends on: the shapes (num_envs, rollout_size), which rank's
 envs and draws these are, and every option that decides which state exists or how the next rollout and update read it.  A run
-resumes a state only under exactly these values; to change one, start from the weights alone (`--load_path`).  Nothing here
+resumes a state only under exactly these values; to change one, start from the weights alone (`--load_path`).  `meta_ext`
+holds the options that came after format 1 (`lambda_returns`), under the same rule; a file written before them has no such
+block and resumes as a run with those options at their defaults -- so the format number did not have to move.  Nothing here
 touches a GPU: `check_meta` runs in `PPO.__init__` before the env exists.
 """
 import os
@@ -22,6 +24,9 @@ FORMAT = 1
 META_FIELDS = ("num_envs", "rollout_size", "variant", "reward", "world_size", "rank", "gae", "minibatch", "minibatch_seed",
                "action_noise", "noise_rho", "normalize_obs", "obs_clip", "normalize_value", "normalize_advantage", "randomize",
                "dr_ranges", "dr_seed", "gemm", "step_gemm", "persistent_rollout", "dp_mode")
+# Options added after format 1 was fixed: their own top-level block of the file, "meta_ext", checked as strictly as `meta`.  A
+# file without the block (or without a field) was written before the option existed, so it holds the option's default.
+META_EXT_FIELDS = ("lambda_returns",)
 
 
 def training_state_path(weights_path, rank):
@@ -61,6 +66,26 @@ def compare_meta(file_meta, run_meta):
 def check_meta(file_meta, args):
     """The meta check: the file's meta and the resuming run's args go in, it returns or raises ValueError."""
     compare_meta(file_meta, expected_meta(args))
+
+
+def expected_meta_ext(args):
+    """The meta_ext block of the run that `args` describes: the resolved record, projected onto META_EXT_FIELDS."""
+    meta = options.projection(options.resolve(args, os.environ))
+    return {field: meta[field] for field in META_EXT_FIELDS}
+
+
+def check_meta_ext(file_ext, args):
+    """The meta_ext check, strict as compare_meta: `file_ext` is the file's meta_ext block, or None for a file that has none,
+    `args` the resuming run's.  Every field of META_EXT_FIELDS must equal the run's -- a field the file lacks reads as the
+    option's default -- else ValueError naming the first that does not, with both values."""
+    if file_ext is not None and not isinstance(file_ext, dict):
+        raise ValueError("training state: meta_ext is no block")
+    run_ext = expected_meta_ext(args)
+    for field in META_EXT_FIELDS:
+        held = (file_ext or {}).get(field, options.BY_NAME[field].default)
+        if held != run_ext[field] or type(held) is not type(run_ext[field]):
+            raise ValueError("training state: %s is %r in the state file and %r in this run; a state resumes only under the "
+                             "options it was saved with (--load_path takes the weights alone)" % (field, held, run_ext[field]))
 
 
 def check_format(state):

@@ -242,6 +242,23 @@ int ppo_value_norm_merge(const double* stats_in, const double* sets, int64_t k, 
                          void* stream);
 int ppo_value_norm_apply(const float* target, int64_t n, const float* table, float* out, void* stream);
 
+/* λ-return critic targets (opt-in, PPO --lambda_returns).  NOT the reference's critic target (the
+ * one-step TD target of ppo.py:160): the critic regresses on A_t + V(s_t), rl_games' / SB3's / cleanrl's `returns`.  A
+ * stand-alone pass behind any of the GAE entry points above, over the advantages they wrote and the critic outputs they read.
+ * ppo_lambda_targets: per element i < n, in separately rounded fp32 ops in this order, no fma:
+ *     vd = table ? v[i] * s + m : v[i]        (table f32 [FLY_VALUE_NORM_TABLE] = m | s | r | 0: ppo_td_gae_vnorm's denormalisation)
+ *     target_out[i] = adv[i] + vd             (NaN passes through)
+ *   float32 numpy reproduces it bit for bit.  A row where the estimator left adv = 0 (a stale row of ppo_td_gae_episodic) gets
+ *   vd; a fall gets adv + vd with no bootstrap, because adv has none; the reference estimator's quirks pass through unchanged.
+ *   With sets != NULL also the float64 moments (count | mean | M2) of all n targets, one set per workgroup in
+ *   sets f64 [FLY_VALUE_NORM_SETS][FLY_VALUE_NORM_SET] (sets over nothing have count 0): per-lane Welford updates and a fixed
+ *   combination tree, no atomics, deterministic -- what ppo_td_gae_vnorm hands ppo_value_norm_merge.  sets == NULL writes none.
+ *   One launch, no host sync.  16-byte accesses when adv, v and target_out are all 16-byte aligned, a scalar path with identical
+ *   results otherwise.  target_out must not alias adv or v.  n == 0 writes no target (and empty sets); n < 0 or a NULL adv, v or
+ *   target_out is FLY_E_ARG. */
+int ppo_lambda_targets(const float* adv, const float* v, const float* table, int64_t n, float* target_out, double* sets,
+                       void* stream);
+
 /* Episode-aware advantage estimate (opt-in, PPO --gae episodic).  NOT the reference's estimator
  * (ppo.py:157-171, PPO_GAE_COMPAT): per-step end flags, a recurrence that stops at every episode end, a bootstrap through
  * time-outs, and no training signal from the step in which the env performs its reset.  reset and progress are the int64

@@ -12,6 +12,13 @@ loaded with it; such a checkpoint needs `--normalize_obs` to load.
 `--normalize_value` (running mean / std normalisation of the critic's regression targets; off by default): the critic's
 outputs are mapped back to reward units wherever they meet rewards; the statistics are saved with the checkpoint as
 value_rms.* and loaded with it; such a checkpoint needs `--normalize_value` to load.
+`--lambda_returns` (the critic regresses on the lambda-return A_t + V(s_t) of the advantage estimator in use, DESIGN.md 3.3g;
+off by default: the reference's one-step TD target r + gamma v(s')).  The policy's advantages are untouched; with
+`--normalize_value` the running statistics are those of the lambda-returns.  Meant for `--gae episodic`: the reference
+estimator's quirks pass through, and its done mask makes whole columns of lambda-returns strongly negative.  One seed of
+evidence (profiles/lambda_returns_curve.txt): under the reference's hyper-parameters it does not train the standing task.
+Nothing of it goes into the weights file;
+`--save_state` records the option, and a state resumes only under the value it was saved with.
 `--gae episodic` (episode-aware advantage estimate with time-limit bootstrapping; the default `reference` is
 the reference's estimator with its quirks).
 `--minibatch shuffled` (every epoch draws its 15 minibatches from a fresh permutation of ALL rows of the rollout, DESIGN.md
@@ -104,6 +111,13 @@ def parse_args(argv=None):
          help='the critic regresses on TD targets normalised by their running mean / std, and its outputs are '
               'mapped back to reward units for the TD target and GAE (rl_games normalize_value, without its clamp; '
               'not in the reference; off by default)')
+    flag('lambda_returns', action='store_true',
+         help='the critic regresses on the lambda-return A_t + V(s_t) (the GAE advantage, before any normalisation, plus the '
+              'critic\'s own value in reward units: rl_games / SB3 / cleanrl `returns`) instead of the one-step TD target '
+              'r + gamma v(s\') of ppo.py:160; with --normalize_value the running statistics are those of the lambda-returns.  '
+              'NOT the reference\'s critic target; off by default.  Meant for --gae episodic (the reference estimator\'s '
+              'done-mask quirk passes through and is amplified); on one seed it did not train the standing task under the '
+              'reference\'s hyper-parameters (DESIGN.md 3.3g)')
     flag('gae', type=str,
          help='advantage estimator: reference = ppo.py:157-171 as it stands (the done mask of the last step over the '
               'whole rollout, no reset of the recurrence at episode ends); episodic = per-step end flags, the '
