@@ -34,6 +34,8 @@ OBS_NORM_SETS = 256     # FLY_OBS_NORM_SETS: moment sets one ppo_obs_norm_pass w
 VALUE_NORM_SET = 3      # FLY_VALUE_NORM_SET: count | mean | var or M2 (f64)
 VALUE_NORM_TABLE = 4    # FLY_VALUE_NORM_TABLE: m | s | r | 0 (f32)
 VALUE_NORM_SETS = 256   # FLY_VALUE_NORM_SETS: moment sets one ppo_td_gae_vnorm writes
+EPISODE_SET = 10        # FLY_EPISODE_SET: n | ret_mean | ret_M2 | ret_min | ret_max | len_sum | len_min | len_max | timeouts | rows (f64)
+EPISODE_SETS = 256      # FLY_EPISODE_SETS: sets one ppo_episode_stats writes
 DR_PARAMS = 6           # FLY_DR_PARAMS: kp, kd, effort, mass (+ inertia), mu, gravity multipliers
 DR_ROW = 8              # FLY_DR_ROW: a randomisation table row, f32 m[6] | draw count (int32 bits) | 0
 ABI_VERSION = 13        # include/flyhip.h as this package binds it (fly_abi_version(): argument lists changed between versions)
@@ -65,6 +67,8 @@ SYMBOLS = {
     "ppo_lambda_targets": [_P, _P, _P, _L, _P, _P, _P],
     "ppo_td_gae_episodic": [_P, _P, _P, _P, _P, _P, _L, _F, _F, _L, _L, _P, _P, _I, _P],
     "ppo_td_gae_episodic_vnorm": [_P, _P, _P, _P, _P, _P, _L, _P, _F, _F, _L, _L, _P, _P, _P, _I, _P],
+    "ppo_episode_stats": [_P, _P, _P, _L, _L, _L, _P, _P, _P, _I, _P],
+    "ppo_episode_stats_merge": [_P, _L, _P, _P, _P],
     "ppo_minibatch_gather": [_P] * 5 + [_L, C.c_uint32, C.c_uint32, _L, _L] + [_P] * 6 + [_P],
     "ppo_noise_ar1": [_P, _P, _L, _L, _F, _P],
     "ppo_step_bookkeeping": [_P, _L, _P, _F, _P, _I, _F, _F, _P],

@@ -350,6 +350,38 @@ int ppo_td_gae_episodic_vnorm(const float* reward, const float* v, const float* 
     return FLY_OK;
 }
 
+int ppo_episode_stats(const float* reward, const int64_t* reset, const int64_t* progress, int64_t max_episode_length, int64_t T,
+                      int64_t N, double* carry_ret, int64_t* carry_len, double* sets, int mode_flags, void* stream)
+{
+    int rc = check_episodic("ppo_episode_stats", !reward || !reset || !progress || !carry_ret || !carry_len || !sets,
+                            max_episode_length, T, N, mode_flags);
+    if (rc) return rc;
+    if (T > (INT64_MAX >> 3) / N) return fail(FLY_E_ARG, "ppo_episode_stats: T * N int64 rows overflow a byte offset");
+    if (reinterpret_cast<uintptr_t>(reward) & 3) return fail(FLY_E_ARG, "ppo_episode_stats: reward is not 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(reset) | reinterpret_cast<uintptr_t>(progress) | reinterpret_cast<uintptr_t>(carry_ret) |
+         reinterpret_cast<uintptr_t>(carry_len) | reinterpret_cast<uintptr_t>(sets)) & 7)
+        return fail(FLY_E_ARG, "ppo_episode_stats: an int64 / float64 buffer is not 8-byte aligned");
+    hipError_t e = flyhip_launch_episode_stats(reward, reset, progress, max_episode_length, T, N, carry_ret, carry_len, sets,
+                                               mode_flags, stream);
+    if (e != hipSuccess) return hip_fail(e, "ppo_episode_stats launch");
+    return FLY_OK;
+}
+
+int ppo_episode_stats_merge(const double* sets, int64_t nsets, double* window, double* total, void* stream)
+{
+    if (!sets || !window || !total) return fail(FLY_E_ARG, "ppo_episode_stats_merge: null pointer");
+    if (nsets <= 0) return fail(FLY_E_ARG, "ppo_episode_stats_merge: nsets must be > 0");
+    if (nsets > INT64_MAX / (FLY_EPISODE_SET * (int64_t)sizeof(double)))
+        return fail(FLY_E_ARG, "ppo_episode_stats_merge: nsets * FLY_EPISODE_SET overflows int64");
+    if ((reinterpret_cast<uintptr_t>(sets) | reinterpret_cast<uintptr_t>(window) | reinterpret_cast<uintptr_t>(total)) & 7)
+        return fail(FLY_E_ARG, "ppo_episode_stats_merge: a float64 buffer is not 8-byte aligned");
+    if (window < total + FLY_EPISODE_SET && total < window + FLY_EPISODE_SET)
+        return fail(FLY_E_ARG, "ppo_episode_stats_merge: window must not overlap total");
+    hipError_t e = flyhip_launch_episode_stats_merge(sets, nsets, window, total, stream);
+    if (e != hipSuccess) return hip_fail(e, "ppo_episode_stats_merge launch");
+    return FLY_OK;
+}
+
 int ppo_minibatch_gather(const float* obs, const float* act, const float* logp, const float* adv, const float* target, int64_t R,
                          uint32_t seed, uint32_t epoch_key, int64_t first, int64_t n, float* obs_out, float* act_out,
                          float* logp_out, float* adv_out, float* target_out, int32_t* index_out, void* stream)

@@ -65,6 +65,12 @@ hipError_t flyhip_launch_td_gae_episodic_vnorm(const float* reward, const float*
                                                const float* table, float gamma, float lambda, int64_t T, int64_t N,
                                                float* target_out, float* adv_out, double* sets, int mode, void* stream);
 
+// episode_stats.hip
+hipError_t flyhip_launch_episode_stats(const float* reward, const int64_t* reset, const int64_t* progress,
+                                       int64_t max_episode_length, int64_t T, int64_t N, double* carry_ret, int64_t* carry_len,
+                                       double* sets, int mode, void* stream);
+hipError_t flyhip_launch_episode_stats_merge(const double* sets, int64_t nsets, double* window, double* total, void* stream);
+
 // minibatch_gather.hip
 hipError_t flyhip_launch_minibatch_gather(const float* obs, const float* act, const float* logp, const float* adv,
                                           const float* target, int64_t R, uint32_t seed, uint32_t epoch_key, int64_t first,

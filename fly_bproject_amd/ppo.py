@@ -217,6 +217,12 @@ class PPO:
             # the end flags the env carries into the first rollout: its initial reset_buf (every env resets in its first step)
             self._flag_rows()
             self._ended_prev = self.env.reset_buf.clone()
+        # opt-in (`episode_stats`): return and length of the episodes that finish, from the reward and flag rows at the end of
+        # every rollout, on the score line and through episode_stats().  It observes: nothing the rollout or
+        # the update reads is written.
+        self._episode_stats = opts.episode_stats
+        if self._episode_stats:
+            self._setup_episode_stats()
         # opt-in (`minibatch="shuffled"`): every epoch draws its 15 minibatches from a fresh keyed permutation of ALL T * N rows
         # of the rollout, gathered into one staging set in front of the unchanged optimizer-step kernels.  NOT
         # the reference's contiguous-in-time slices (Q3).  Nothing of it goes into the weights file; `--save_state` carries it
@@ -535,6 +541,63 @@ class PPO:
             p(self.all_reward), p(values[:T]), p(values[1:]), p(self._reset_rows), p(self._progress_rows), p(self._ended_prev),
             C.c_int64(self.env.max_episode_length), C.c_float(self.gamma), C.c_float(self.lmbda), C.c_int64(T), C.c_int64(n),
             p(self._target), p(self.all_advantage), C.c_int(mode), _lib.stream_ptr()), "ppo_td_gae_episodic")
+
+    # ------------------------------------------------------------------------------------------
+    # episode statistics (opt-in)
+    def _setup_episode_stats(self):
+        """The per-env carries of the open episodes (float64 return, int64 length), the sets one ppo_episode_stats launch
+        writes, and the two persistent sets: `window` (episodes closed since the last score line) and `total` (since the start
+        of the run), both the empty set with rows = 0."""
+        dev, n = self.device, int(self.args.num_envs)
+        self._flag_rows()
+        self._ep_carry_ret = torch.zeros(n, dtype=torch.float64, device=dev)
+        self._ep_carry_len = torch.zeros(n, dtype=torch.long, device=dev)
+        self._ep_sets = torch.zeros((_lib.EPISODE_SETS, _lib.EPISODE_SET), dtype=torch.float64, device=dev)
+        inf = float("inf")
+        self._ep_empty = torch.tensor([0.0, 0.0, 0.0, inf, -inf, 0.0, inf, 0.0, 0.0, 0.0], dtype=torch.float64, device=dev)
+        self._ep_window, self._ep_total = self._ep_empty.clone(), self._ep_empty.clone()
+
+    def _episode_stats_pass(self):
+        """The finished rollout's rows through ppo_episode_stats (the carries go on into the next rollout), all ranks' sets in
+        rank order into `window` and `total` (ppo_episode_stats_merge): every rank holds the same two sets.  On the stream, no
+        host sync."""
+        T, n = self.rollout_size, int(self.args.num_envs)
+        mode = 4 if n < 512 and T >= 1024 else 0                    # PPO_GAE_SCAN: make_data's rule
+        _lib.check(self._lib.ppo_episode_stats(
+            p(self.all_reward), p(self._reset_rows), p(self._progress_rows), C.c_int64(self.env.max_episode_length), C.c_int64(T),
+            C.c_int64(n), p(self._ep_carry_ret), p(self._ep_carry_len), p(self._ep_sets), C.c_int(mode), _lib.stream_ptr()),
+            "ppo_episode_stats")
+        sets = self._all_rank_sets(self._ep_sets, "_keep_ep_sets")
+        _lib.check(self._lib.ppo_episode_stats_merge(p(sets), C.c_int64(sets.shape[0]), p(self._ep_window), p(self._ep_total),
+                                                     _lib.stream_ptr()), "ppo_episode_stats_merge")
+
+    @staticmethod
+    def _episode_suffix(w):
+        """' | Episodes ...' of the score line from a set's ten numbers."""
+        n = int(w[0])
+        if n == 0:
+            return " | Episodes 0"
+        return " | Episodes {} | Return {:.4f} [{:.4f}, {:.4f}] | Length {:.1f} | Timeouts {:.1f}%".format(
+            n, float(w[1]), float(w[3]), float(w[4]), float(w[5]) / n, 100.0 * float(w[8]) / n)
+
+    def episode_stats(self):
+        """{"window": {...}, "total": {...}}: the episodes closed since the last score line and since the start of the run, as
+        Python numbers (episodes, return_mean, return_std -- the population's --, return_min, return_max, length_mean,
+        length_min, length_max, timeouts; without an episode everything but the two counts is nan).  Host-synchronising.
+        None when `episode_stats` is off."""
+        if not self._episode_stats:
+            return None
+
+        def entries(s):
+            n = int(s[0])
+            if n == 0:
+                nan = float("nan")
+                return {"episodes": 0, "return_mean": nan, "return_std": nan, "return_min": nan, "return_max": nan,
+                        "length_mean": nan, "length_min": nan, "length_max": nan, "timeouts": 0}
+            return {"episodes": n, "return_mean": s[1], "return_std": (max(s[2], 0.0) / n) ** 0.5 if s[2] == s[2] else s[2],
+                    "return_min": s[3], "return_max": s[4], "length_mean": s[5] / n, "length_min": int(s[6]),
+                    "length_max": int(s[7]), "timeouts": int(s[8])}
+        return {"window": entries(self._ep_window.tolist()), "total": entries(self._ep_total.tolist())}
 
     # ------------------------------------------------------------------------------------------
     @property
@@ -963,7 +1026,7 @@ class PPO:
             rc |= lib.fly_step(env._handle, C.c_void_p(self._act_rows[t].data_ptr()), C.byref(env._bufs), st)  # ppo.py:223
         if rc:
             _lib.check(rc, "rollout step")
-        if self.gae == "episodic":
+        if self.gae == "episodic" or self._episode_stats:
             # row t of the flag rows, as the one-launch rollout writes them itself (captured with the step in a graph)
             self._reset_rows[t].copy_(env.reset_buf)
             self._progress_rows[t].copy_(env.progress_buf)
@@ -1041,16 +1104,25 @@ class PPO:
             self._drain_log(block=True)
             score = float(self._score_acc.item())
             self._score_acc.zero_()
+            if self._episode_stats:
+                suffix += self._episode_suffix(self._ep_window.tolist())
+                self._ep_window.copy_(self._ep_empty)
             if rank0:
                 print(self.SCORE_LINE.format(self.run_step, self.optim_step, score, self._action_var[0].item()) + suffix)
             return
         dev_vals = torch.stack((self._score_acc.reshape(()), self._action_var[0]))
         host = torch.empty(2, dtype=torch.float32, pin_memory=True)
         host.copy_(dev_vals, non_blocking=True)
+        window = None
+        if self._episode_stats:
+            # the window's ten float64 numbers by the same route; the window starts anew on the stream, behind the copy
+            window = torch.empty(_lib.EPISODE_SET, dtype=torch.float64, pin_memory=True)
+            window.copy_(self._ep_window, non_blocking=True)
+            self._ep_window.copy_(self._ep_empty)
         ev = torch.cuda.Event()
         ev.record()
         self._score_acc.zero_()
-        self._log_q.append((ev, host, dev_vals, self.run_step, self.optim_step, rank0, suffix))
+        self._log_q.append((ev, host, dev_vals, self.run_step, self.optim_step, rank0, suffix, window))
         self._drain_log()
 
     def _drain_log(self, block=False):
@@ -1061,11 +1133,13 @@ class PPO:
             if isinstance(head, str):
                 print(head)
             else:
-                ev, host, _keep, run_step, optim_step, rank0, suffix = head
+                ev, host, _keep, run_step, optim_step, rank0, suffix, window = head
                 if block:
                     ev.synchronize()
                 elif not ev.query():
                     return
+                if window is not None:
+                    suffix += self._episode_suffix(window.tolist())
                 if rank0:
                     print(self.SCORE_LINE.format(run_step, optim_step, float(host[0]), float(host[1])) + suffix)
             q.popleft()
@@ -1145,6 +1219,9 @@ class PPO:
                     rec.flush()                                     # before the next rollout overwrites the record
 
         if t + 1 == self.rollout_size:                              # ppo.py:240-252
+            if self._episode_stats:
+                with torch.no_grad():
+                    self._episode_stats_pass()                      # the rollout's rows are complete; in testing too
             self._flush_bookkeeping()                               # the update reads the decayed variance
             if not self.args.testing:
                 self._emit("Training")
@@ -1248,6 +1325,8 @@ class PPO:
         if self.normalize_value:
             for k in ("value_stats", "value_table", "value_stats_next", "value_table_next"):
                 agent[k] = pack(getattr(self, "_" + k))
+        if self._episode_stats:
+            agent["episode_stats"] = {k: pack(getattr(self, "_ep_" + k)) for k in ("carry_ret", "carry_len", "window", "total")}
         state = {"format": train_state.FORMAT, "meta": self._training_state_meta(),
                  "meta_ext": train_state.expected_meta_ext(self.args), "policy": self.policy.training_state(),
                  "agent": agent, "env": self.env.training_state()}
@@ -1309,6 +1388,20 @@ class PPO:
         if self.normalize_value:
             for k in ("value_stats", "value_table", "value_stats_next", "value_table_next"):
                 restore(getattr(self, "_" + k), agent, "agent", k)
+        if self._episode_stats:
+            if isinstance(agent.get("episode_stats"), dict):
+                for k in ("carry_ret", "carry_len", "window", "total"):
+                    restore(getattr(self, "_ep_" + k), agent["episode_stats"], "agent.episode_stats", k)
+            else:
+                # a state saved without the flag: the env's step count is the open episodes' length (an env whose end flag is
+                # up has no open episode: its count is reset in the step to come), their return so far is gone
+                with torch.no_grad():
+                    self._ep_carry_len.copy_(self.env.progress_buf * (self.env.reset_buf == 0))
+                    self._ep_carry_ret.zero_()
+                    self._ep_window.copy_(self._ep_empty)
+                    self._ep_total.copy_(self._ep_empty)
+                print("episode_stats: the training state holds no episode statistics; each env's first closed return after "
+                      "the resume is partial (its length is whole)")
         self._rate_mark = None
         torch.cuda.synchronize(self.device)
 

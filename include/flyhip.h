@@ -60,6 +60,9 @@ extern "C" {
 #define FLY_VALUE_NORM_TABLE 4   /* value normalisation table: m | s | r | 0 (f32) */
 #define FLY_VALUE_NORM_SET 3     /* one set of value statistics or moments: count | mean | var or M2 (f64) */
 #define FLY_VALUE_NORM_SETS 256  /* moment sets ppo_td_gae_vnorm writes (one per workgroup) */
+#define FLY_EPISODE_SET 10       /* one set of episode statistics (f64): n | ret_mean | ret_M2 | ret_min | ret_max | len_sum |
+                                    len_min | len_max | timeouts | rows */
+#define FLY_EPISODE_SETS 256     /* sets ppo_episode_stats writes (one per workgroup) */
 #define FLY_DR_PARAMS 6   /* kp, kd, effort, mass (+ inertia), mu, gravity: multipliers of the FlyConfig values */
 #define FLY_DR_ROW 8      /* per-env row of the randomisation table, f32: m[6] | draw count (int32 bits) | 0 */
 
@@ -287,6 +290,31 @@ int ppo_td_gae_episodic_vnorm(const float* reward, const float* v, const float* 
                               const int64_t* progress, const int64_t* ended_prev, int64_t max_episode_length, const float* table,
                               float gamma, float lambda, int64_t T, int64_t N, float* target_out, float* adv_out, double* sets,
                               int mode_flags, void* stream);
+
+/* Episode statistics (opt-in, PPO --episode_stats): return and length of the episodes that finished
+ * in a rollout, from the reward row and the int64 flag rows above.  It observes: nothing the rollout or the update reads is
+ * written.  Per env e, with the carries carry_ret f64 [N] / carry_len int64 [N] living across rollouts, t = 0 .. T-1:
+ *     carry_ret[e] += (double)reward[t][e];  carry_len[e] += 1
+ *     reset[t][e] != 0:  an episode closes with return carry_ret[e], length carry_len[e] and
+ *                        timeout = progress[t][e] >= max_episode_length - 1;  then carry_ret[e] = 0, carry_len[e] = 0
+ *   EVERY step counts, the one in which the env performs its reset too (rl_games' current_rewards convention; that step is
+ *   `stale` for ppo_td_gae_episodic, which trains nothing from it).  So a closed episode's length is progress[t][e] at its end
+ *   row, and per env (sum of closed returns) + carry out - carry in is the float64 sum of its rewards.
+ * A set is FLY_EPISODE_SET doubles: n | ret_mean | ret_M2 | ret_min | ret_max | len_sum | len_min | len_max | timeouts | rows.
+ *   Integer fields are exact integers; rows counts the (t, e) rows a workgroup walked (all sets together: T * N).  The empty
+ *   set is 0 | 0 | 0 | +inf | -inf | 0 | +inf | 0 | 0 | rows.  Returns are folded by float64 Welford updates and Chan et al.'s
+ *   merge in a fixed order, no atomics: the same input gives the same bits.  A NaN reward makes its episode's return NaN;
+ *   after that only the integer fields of the sets and the other envs' carries are specified.
+ * ppo_episode_stats writes sets f64 [FLY_EPISODE_SETS][FLY_EPISODE_SET] (workgroups with no env write the empty set) and the
+ *   carries in place.  mode_flags: 0 (lane = env, t walks forward) or PPO_GAE_SCAN (one wave per env, time on lanes, a
+ *   segmented shuffle scan of the chunk sums: for few envs x very long rollouts; the integer fields are identical, the sums
+ *   are added in another order).  Anything else, a NULL pointer, T or N or max_episode_length <= 0, a misaligned buffer or
+ *   a T * N that overflows: FLY_E_ARG.
+ * ppo_episode_stats_merge: one workgroup folds sets[0 .. nsets) in index order (all ranks' sets in rank order) into one set
+ *   and adds that to the persistent sets `window` (episodes since the caller last reset it) and `total`, in place. */
+int ppo_episode_stats(const float* reward, const int64_t* reset, const int64_t* progress, int64_t max_episode_length,
+                      int64_t T, int64_t N, double* carry_ret, int64_t* carry_len, double* sets, int mode, void* stream);
+int ppo_episode_stats_merge(const double* sets, int64_t nsets, double* window, double* total, void* stream);
 
 /* Shuffled PPO minibatches (opt-in, PPO --minibatch shuffled).  NOT the reference's minibatches
  * (ppo.py:173-202: contiguous slices of the rollout in time order).  A minibatch is a window of a keyed permutation pi of the

@@ -19,6 +19,11 @@ estimator's quirks pass through, and its done mask makes whole columns of lambda
 evidence (profiles/lambda_returns_curve.txt): under the reference's hyper-parameters it does not train the standing task.
 Nothing of it goes into the weights file;
 `--save_state` records the option, and a state resumes only under the value it was saved with.
+`--episode_stats` (return and length of the episodes that finished; off by default): the score line also
+carries ` | Episodes n | Return mean [min, max] | Length mean | Timeouts pct%` over the episodes closed since the previous
+score line, every step of an episode counted, the one that performs the reset too.  It observes and steers nothing: weights
+and rollouts are the same bits with and without it.  `--save_state` carries the open episodes and the totals, and a state
+saved with or without the flag resumes with or without it.
 `--gae episodic` (episode-aware advantage estimate with time-limit bootstrapping; the default `reference` is
 the reference's estimator with its quirks).
 `--minibatch shuffled` (every epoch draws its 15 minibatches from a fresh permutation of ALL rows of the rollout, DESIGN.md
@@ -118,6 +123,11 @@ def parse_args(argv=None):
               'NOT the reference\'s critic target; off by default.  Meant for --gae episodic (the reference estimator\'s '
               'done-mask quirk passes through and is amplified); on one seed it did not train the standing task under the '
               'reference\'s hyper-parameters (DESIGN.md 3.3g)')
+    flag('episode_stats', action='store_true',
+         help='the score line also carries the count, mean / min / max return, mean length and time-out share of the '
+              'episodes that finished since the previous score line (every step of an episode counts, the one that '
+              'performs the reset too: rl_games current_rewards); one kernel over the reward and flag rows at the end of a '
+              'rollout, no host sync; changes nothing the rollout or the update reads (DESIGN.md 3.3h); off by default')
     flag('gae', type=str,
          help='advantage estimator: reference = ppo.py:157-171 as it stands (the done mask of the last step over the '
               'whole rollout, no reset of the recurrence at episode ends); episodic = per-step end flags, the '
