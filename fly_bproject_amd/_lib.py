@@ -7,6 +7,7 @@ from .params import FlyParams
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FLYHIP_LIB") or os.path.join(_HERE, "libflyhip.so")
 _lib = None
+_api = None
 
 
 class FlyHipError(RuntimeError):
@@ -72,11 +73,11 @@ SYMBOLS = {
     "ppo_minibatch_gather": [_P] * 5 + [_L, C.c_uint32, C.c_uint32, _L, _L] + [_P] * 6 + [_P],
     "ppo_noise_ar1": [_P, _P, _L, _L, _F, _P],
     "ppo_step_bookkeeping": [_P, _L, _P, _F, _P, _I, _F, _F, _P],
-    "ppo_rollout_step": [_P, _P, _P, _P, _P, _P, _P, _I, _F, _F, _P, _P, _P, _P, _P, _P],
-    "ppo_rollout_all": [_P, _P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
+    "ppo_rollout_step": [_P, C.POINTER(FlyBuffers), _P, _P, _P, _P, _P, _I, _F, _F, _P, _P, _P, _P, _P, _P],
+    "ppo_rollout_all": [_P, C.POINTER(FlyBuffers), _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
     "ppo_rollout_bookkeeping": [_P, _L, _L, _P, _P, _F, _P, _I, _F, _F, _P, _P],
     "mlp_forward": [_P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P],
-    "mlp_forward_sample": [_P, _P, _P, _L, _P, _P, _I, _F, _F, _P, _P, _P, _P, _P, _P],
+    "mlp_forward_sample": [_P, _P, _P, _L, _P, _P, _I, _F, _F, _P, _P, _P, _P, _P, _P, _P],
     "mlp_grad_workspace_floats": [],
     "mlp_backward_dx": [_P] * 10 + [_L, _F, _F, _P, _P, _P, _P, _P, _P, _P],
     "mlp_forward_backward": [_P] * 4 + [_L] + [_P] * 9 + [_F, _F] + [_P] * 6 + [_I, _P, _P, _P, _I, _P],
@@ -120,7 +121,7 @@ def build(verbose=False):
 
 
 def load():
-    global _lib
+    global _lib, _api
     if _lib is not None:
         return _lib
     if not os.path.exists(LIB_PATH):
@@ -137,8 +138,48 @@ def load():
     if lib.fly_abi_version() != ABI_VERSION:
         raise FlyHipError("stale libflyhip.so (ABI %d, this package was written for %d): rebuild it "
                           "(`make -C fly_bproject_amd/csrc`)" % (lib.fly_abi_version(), ABI_VERSION))
+    _api = _Api()
+    for name in SYMBOLS:
+        setattr(_api, name, _checked(name, getattr(lib, name), lib.fly_last_error))
     _lib = lib
     return lib
+
+
+class _Api:
+    """One checked callable per SYMBOLS entry (api())."""
+
+
+def _checked(name, fn, last_error):
+    """`fn` as the product calls it: an argument with a `data_ptr` method (a tensor) goes as that address, everything else as
+    ctypes takes it under fn.argtypes (None, Python numbers, ctypes instances, byref(...), c_void_p arrays).  An int entry point
+    returns None or raises FlyHipError under its own name; a size query (int64_t) and fly_abi_version return their value."""
+    if fn.restype is not C.c_int or name == "fly_abi_version":      # a value, not a status (and no pointer among the arguments)
+        return fn
+    nargs = len(fn.argtypes)
+    slots = tuple(i for i, t in enumerate(fn.argtypes) if t is C.c_void_p)   # where a tensor can stand: decided once, here
+
+    def call(*args):
+        if len(args) != nargs:
+            raise TypeError("%s takes %d arguments (%d given)" % (name, nargs, len(args)))
+        args = list(args)
+        for i in slots:
+            data_ptr = getattr(args[i], "data_ptr", None)
+            if data_ptr is not None:
+                args[i] = data_ptr()
+        rc = fn(*args)
+        if rc != 0:
+            msg = last_error()
+            raise FlyHipError("%s failed (%d): %s" % (name, rc, msg.decode() if msg else "?"))
+    call.__name__ = call.__qualname__ = name
+    return call
+
+
+def api():
+    """The checked binding: api().f(...) is lib.f(...) with tensors passed as they are and the return code checked.  The stream
+    stays the caller's explicit last argument."""
+    if _api is None:
+        load()
+    return _api
 
 
 def check(rc, what):

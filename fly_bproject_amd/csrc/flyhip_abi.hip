@@ -76,7 +76,7 @@ int launch(FlyHandle h, int phases, const float* actions, const FlyBuffers* b, v
 extern "C" {
 
 const char* fly_last_error(void) { return g_err; }
-int fly_abi_version(void) { return 13; }
+int fly_abi_version(void) { return FLY_ABI_VERSION; }
 
 int fly_create(const FlyConfig* cfg, FlyHandle* out)
 {

@@ -81,9 +81,9 @@ class P2PAllReduce:
         # stage 1: allocate + export, then everybody learns everybody's handle (or that there is none)
         mine, why = None, ""
         try:
-            _lib.check(self._lib.dp_p2p_alloc(C.c_int64(self.n), C.byref(self._mine)), "dp_p2p_alloc")
+            _lib.api().dp_p2p_alloc(self.n, C.byref(self._mine))
             handle = (C.c_uint8 * 64)()
-            _lib.check(self._lib.dp_ipc_export(self._mine, handle), "dp_ipc_export")
+            _lib.api().dp_ipc_export(self._mine, handle)
             mine = bytes(handle)
         except Exception as e:      # noqa: BLE001
             why = "rank %d: %r" % (self.rank, e)
@@ -102,11 +102,11 @@ class P2PAllReduce:
                 else:
                     ptr = C.c_void_p()
                     buf = (C.c_uint8 * 64).from_buffer_copy(h)
-                    _lib.check(self._lib.dp_ipc_import(buf, C.byref(ptr)), "dp_ipc_import (rank %d)" % r)
+                    _lib.api().dp_ipc_import(buf, C.byref(ptr))
                     self._windows[r] = ptr.value
                     self._opened.append(ptr)
         except Exception as e:      # noqa: BLE001
-            ok, why = False, "rank %d: %r" % (self.rank, e)
+            ok, why = False, "rank %d, opening rank %d's window: %r" % (self.rank, r, e)
         votes = [None] * self.world
         dist.all_gather_object(votes, (ok, why), group=group)           # doubles as the barrier: every window is open before anybody publishes
         if not all(v[0] for v in votes):
@@ -130,10 +130,8 @@ class P2PAllReduce:
     def allreduce_(self, t):
         assert t.is_contiguous() and t.dtype == torch.float32 and t.numel() == self.n and t.device == self.device
         self.epoch += 1
-        C = self._C
-        self._libmod.check(self._lib.dp_allreduce_p2p(C.c_void_p(t.data_ptr()), C.c_int64(self.n), self._windows, self.rank,
-                                                      self.world, C.c_uint32(self.epoch), C.c_void_p(self.err.data_ptr()),
-                                                      C.c_int64(self.fail_slot), self._libmod.stream_ptr()), "dp_allreduce_p2p")
+        self._libmod.api().dp_allreduce_p2p(t, self.n, self._windows, self.rank, self.world, self.epoch, self.err, self.fail_slot,
+                                   self._libmod.stream_ptr())
         return t
 
     def check(self):

@@ -23,7 +23,6 @@ are explicit:
   D2  `act()` yields ONE scalar per env (dqn.py:89-100) while `Fly.step` takes 18 joint targets:
       the scalar is broadcast to all 18 DoFs.
 """
-import ctypes as C
 import random
 
 import torch
@@ -291,7 +290,7 @@ class DQN:
         if getattr(self, "_fu_rows", 0) < S * n:
             self._fu_rows = S * n
             # (sized for the bf16x3 launches -- the larger images -- and the fp16x2 workspace -- the larger workspace: either can run)
-            self._fu_images = torch.empty(int(lib.dqn_fused_image_halves(C.c_int64(S * n))), dtype=torch.int16, device=self.device)
+            self._fu_images = torch.empty(int(lib.dqn_fused_image_halves(S * n)), dtype=torch.int16, device=self.device)
             self._fu_ws = torch.empty(max(int(lib.dqn_fused_workspace_floats()), int(lib.dqn_fused_h2_workspace_floats())), device=self.device)
             self._fu_loss = torch.zeros(tiles, device=self.device)
         if getattr(self, "_fu_S", 0) < S:
@@ -347,20 +346,18 @@ class DQN:
         return dev, aligned
 
     def _fused_launch(self, dev, S, n, aligned, inv_B):
-        pk, lib = self.packed, self._lib
+        pk = self.packed
         loss_part = self._fu_loss[:S * n // 32]
-        _lib.check(lib.dqn_fused_update(p(pk.P), p(pk.QB), p(pk.QTB), p(pk.P_tgt), p(pk.QB_tgt), p(dev), C.c_int(S), C.c_int64(n),
-                                        C.c_float(self.discount), C.c_float(inv_B), p(self._fu_images), p(self._fu_ws), p(pk.G),
-                                        p(loss_part), C.c_int(aligned), _lib.stream_ptr()), "dqn_fused_update")
+        _lib.api().dqn_fused_update(pk.P, pk.QB, pk.QTB, pk.P_tgt, pk.QB_tgt, dev, S, n, self.discount, inv_B, self._fu_images,
+                                   self._fu_ws, pk.G, loss_part, aligned, _lib.stream_ptr())
         return loss_part
 
     def _fused_launch_h2(self, dev, S, n, aligned, inv_B, flags):
-        pk, lib = self.packed, self._lib
+        pk = self.packed
         loss_part = self._fu_loss[:S * n // 32]
-        _lib.check(lib.dqn_fused_update_h2(p(pk.P), p(pk.QH), p(pk.QTH), p(pk.P_tgt), p(pk.QH_tgt), p(pk.idx_fb), p(pk.idx_tb),
-                                           p(pk.h2_scales), p(pk.h2_overflow), p(dev), C.c_int(S), C.c_int64(n), C.c_float(self.discount),
-                                           C.c_float(inv_B), p(self._fu_images), p(self._fu_ws), p(pk.G), p(loss_part), C.c_int(aligned),
-                                           C.c_int(flags), _lib.stream_ptr()), "dqn_fused_update_h2")
+        _lib.api().dqn_fused_update_h2(pk.P, pk.QH, pk.QTH, pk.P_tgt, pk.QH_tgt, pk.idx_fb, pk.idx_tb, pk.h2_scales, pk.h2_overflow,
+                                      dev, S, n, self.discount, inv_B, self._fu_images, self._fu_ws, pk.G, loss_part, aligned, flags,
+                                      _lib.stream_ptr())
         return loss_part
 
     def update(self, chunks=None):
@@ -372,7 +369,7 @@ class DQN:
             chunks = self.replay.sample(self.mini_batch_size)
         self._updates_issued += 1
         self._h2_guard = False
-        pk, lib = self.packed, self._lib
+        pk, api = self.packed, _lib.api()
         st = _lib.stream_ptr()
         B = sum(int(c[0].shape[0]) for c in chunks)
         inv_B = 1.0 / float(B)
@@ -382,11 +379,9 @@ class DQN:
                 for t in c:
                     assert t.is_contiguous() and t.dtype == torch.float32
             loss_part = self._update_fused(chunks, inv_B, lazy)
-            guard = p(pk.h2_overflow) if self._h2_guard else None
-            _lib.check(lib.dqn_adam_soft_update(p(pk.P), p(pk.PF), p(pk.PT), p(pk.P_tgt), p(pk.PF_tgt), p(pk.idx_f), p(pk.idx_t),
-                                                p(pk.G), p(pk.grad_mask), p(pk.exp_avg), p(pk.exp_avg_sq), p(pk.step),
-                                                C.c_float(self.lr), C.c_float(0.9), C.c_float(0.999), C.c_float(1e-8),
-                                                C.c_float(self.tau), *pk.plane_args(), guard, st), "dqn_adam_soft_update")
+            guard = pk.h2_overflow if self._h2_guard else None
+            api.dqn_adam_soft_update(pk.P, pk.PF, pk.PT, pk.P_tgt, pk.PF_tgt, pk.idx_f, pk.idx_t, pk.G, pk.grad_mask, pk.exp_avg,
+                                     pk.exp_avg_sq, pk.step, self.lr, 0.9, 0.999, 1e-8, self.tau, *pk.plane_args(), guard, st)
             if self._h2_guard:
                 self._h2_watch()
             return loss_part.sum() * inv_B
@@ -398,17 +393,12 @@ class DQN:
             n = int(obs.shape[0])
             for t in (obs, act, reward, next_obs, done_mask):
                 assert t.is_contiguous() and t.dtype == torch.float32
-            _lib.check(lib.dqn_td_step(p(pk.P), p(pk.PF), p(pk.PT), p(pk.P_tgt), p(pk.PF_tgt), p(obs), p(next_obs), p(act),
-                                       p(reward), p(done_mask), C.c_int64(n), C.c_float(self.discount), C.c_float(inv_B),
-                                       p(self._h1), p(self._h2), p(self._dz3), p(self._dz2), p(self._dz1), p(self._loss_part[i]),
-                                       st), "dqn_td_step")
-            _lib.check(lib.dqn_grad_w(p(obs), p(self._h1), p(self._h2), p(self._dz1), p(self._dz2), p(self._dz3), C.c_int64(n),
-                                      p(self._gw_ws), p(pk.G), C.c_int((1 if i else 0) | (2 if i == len(chunks) - 1 else 0)), st),
-                       "dqn_grad_w")
-        _lib.check(lib.dqn_adam_soft_update(p(pk.P), p(pk.PF), p(pk.PT), p(pk.P_tgt), p(pk.PF_tgt), p(pk.idx_f), p(pk.idx_t),
-                                            p(pk.G), p(pk.grad_mask), p(pk.exp_avg), p(pk.exp_avg_sq), p(pk.step),
-                                            C.c_float(self.lr), C.c_float(0.9), C.c_float(0.999), C.c_float(1e-8),
-                                            C.c_float(self.tau), *pk.plane_args(), None, st), "dqn_adam_soft_update")
+            api.dqn_td_step(pk.P, pk.PF, pk.PT, pk.P_tgt, pk.PF_tgt, obs, next_obs, act, reward, done_mask, n, self.discount, inv_B,
+                            self._h1, self._h2, self._dz3, self._dz2, self._dz1, self._loss_part[i], st)
+            api.dqn_grad_w(obs, self._h1, self._h2, self._dz1, self._dz2, self._dz3, n, self._gw_ws, pk.G,
+                           (1 if i else 0) | (2 if i == len(chunks) - 1 else 0), st)
+        api.dqn_adam_soft_update(pk.P, pk.PF, pk.PT, pk.P_tgt, pk.PF_tgt, pk.idx_f, pk.idx_t, pk.G, pk.grad_mask, pk.exp_avg,
+                                 pk.exp_avg_sq, pk.step, self.lr, 0.9, 0.999, 1e-8, self.tau, *pk.plane_args(), None, st)
         return self._loss_part.sum() * inv_B                              # F.smooth_l1_loss: mean over the batch
 
     def q_parameters(self):
@@ -419,8 +409,7 @@ class DQN:
         x = obs.reshape(-1, IN)
         x = x if x.is_contiguous() else x.contiguous()
         out = torch.empty((x.shape[0], NACT), device=self.device)
-        _lib.check(self._lib.dqn_forward(p(self.packed.P), p(self.packed.PF), p(x), C.c_int64(x.shape[0]), p(out),
-                                         _lib.stream_ptr()), "dqn_forward")
+        _lib.api().dqn_forward(self.packed.P, self.packed.PF, x, x.shape[0], out, _lib.stream_ptr())
         return out
 
     def act(self, obs, epsilon=0.0):
@@ -430,8 +419,7 @@ class DQN:
         self._rand.uniform_(generator=self._gen)
         x = obs if obs.is_contiguous() else obs.contiguous()
         out = torch.empty(n, device=obs.device)
-        _lib.check(self._lib.dqn_act(p(self.packed.P), p(self.packed.PF), p(x), C.c_int64(n), p(self._coin), p(self._rand),
-                                     C.c_float(epsilon), p(out), None, _lib.stream_ptr()), "dqn_act")
+        _lib.api().dqn_act(self.packed.P, self.packed.PF, x, n, self._coin, self._rand, epsilon, out, None, _lib.stream_ptr())
         return out
 
     def run(self):

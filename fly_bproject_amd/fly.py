@@ -71,7 +71,7 @@ class Fly:
         self._lib = _lib.load()
         torch.cuda.set_device(self.device)
         self._handle = C.c_void_p()
-        _lib.check(self._lib.fly_create(C.byref(self.params), C.byref(self._handle)), "fly_create")
+        _lib.api().fly_create(C.byref(self.params), C.byref(self._handle))
 
         dev = self.device
         f32 = dict(dtype=torch.float32, device=dev)
@@ -169,7 +169,7 @@ class Fly:
         every reset the kernels perform then draws that env's next set.  `None` turns it off: the plain kernels run again and
         the table is left as it is."""
         if ranges is None:
-            _lib.check(self._lib.fly_set_randomization(self._handle, None, None, _lib.stream_ptr()), "fly_set_randomization")
+            _lib.api().fly_set_randomization(self._handle, None, None, _lib.stream_ptr())
             self._dr_on = False
             self.launch_form += 1
             return
@@ -179,8 +179,7 @@ class Fly:
         r = _lib.FlyRandomization()
         r.lo[:], r.hi[:] = lo, hi
         r.seed = int(seed) % (1 << 32)
-        _lib.check(self._lib.fly_set_randomization(self._handle, C.byref(r), C.c_void_p(self._dr_table.data_ptr()),
-                                                   _lib.stream_ptr()), "fly_set_randomization")
+        _lib.api().fly_set_randomization(self._handle, C.byref(r), self._dr_table, _lib.stream_ptr())
         self._dr_on = True
         self.launch_form += 1
 
@@ -231,8 +230,7 @@ class Fly:
         a = self._check_actions(actions)
         rec = self.recorder
         row = rec.next_ring_row() if rec is not None else 0
-        _lib.check(self._lib.fly_step(self._handle, C.c_void_p(a.data_ptr()), C.byref(self._bufs),
-                                      _lib.stream_ptr()), "fly_step")
+        _lib.api().fly_step(self._handle, a, C.byref(self._bufs), _lib.stream_ptr())
         if rec is not None:
             rec.capture(row)
             rec.reached(row, self.render_count)
@@ -241,36 +239,31 @@ class Fly:
     def set_actions(self, actions):
         """fly.py:626-657 alone: scale to joint ranges and hand the targets to the sim."""
         a = self._check_actions(actions)
-        _lib.check(self._lib.fly_scale_actions(self._handle, C.c_void_p(a.data_ptr()),
-                                               C.c_void_p(self.actions.data_ptr()), _lib.stream_ptr()),
-                   "fly_scale_actions")
+        _lib.api().fly_scale_actions(self._handle, a, self.actions, _lib.stream_ptr())
 
     def reset(self):
         """fly.py:446-480.  Returns whether any env was flagged (one host sync, as upstream)."""
         any_flag = bool(self.reset_buf.any().item())
         if not any_flag:
             return False
-        _lib.check(self._lib.fly_reset_masked(self._handle, C.byref(self._bufs), _lib.stream_ptr()),
-                   "fly_reset_masked")
+        _lib.api().fly_reset_masked(self._handle, C.byref(self._bufs), _lib.stream_ptr())
         return True
 
     def reset_async(self):
         """fly.py:446-480 without the host sync of the boolean return value."""
-        _lib.check(self._lib.fly_reset_masked(self._handle, C.byref(self._bufs), _lib.stream_ptr()),
-                   "fly_reset_masked")
+        _lib.api().fly_reset_masked(self._handle, C.byref(self._bufs), _lib.stream_ptr())
 
     def simulate(self):
         """fly.py:482-485."""
-        _lib.check(self._lib.fly_integrate(self._handle, C.byref(self._bufs), _lib.stream_ptr()), "fly_integrate")
+        _lib.api().fly_integrate(self._handle, C.byref(self._bufs), _lib.stream_ptr())
 
     def get_obs(self):
         """fly.py:397-411."""
-        _lib.check(self._lib.fly_pack_obs(self._handle, C.byref(self._bufs), _lib.stream_ptr()), "fly_pack_obs")
+        _lib.api().fly_pack_obs(self._handle, C.byref(self._bufs), _lib.stream_ptr())
 
     def get_reward(self):
         """fly.py:413-443."""
-        _lib.check(self._lib.fly_pack_reward(self._handle, C.byref(self._bufs), 0, _lib.stream_ptr()),
-                   "fly_pack_reward")
+        _lib.api().fly_pack_reward(self._handle, C.byref(self._bufs), 0, _lib.stream_ptr())
 
     compute_observations = get_obs      # names used by BASELINE.json's north_star
     compute_reward = get_reward
@@ -348,7 +341,7 @@ class Fly:
             self.recorder.close()
         if self._handle:
             torch.cuda.synchronize(self.device)
-            _lib.check(self._lib.fly_destroy(self._handle), "fly_destroy")
+            _lib.api().fly_destroy(self._handle)
             self._handle = C.c_void_p()
 
     def __del__(self):

@@ -146,8 +146,7 @@ class PackedPolicy:
         safe (mlp_adam_step rescales by itself; this launch also seeds its bookkeeping in the table)."""
         if self.device.type != "cuda":
             return                                  # (layout-only uses of the class on the CPU: tests/test_dist_cpu.py)
-        _lib.check(self._lib.mlp_h2_rescale(p(self.P), p(self.idx_fb), p(self.idx_tb), p(self.PH), p(self.PTH), p(self.h2_scales),
-                                            _lib.stream_ptr()), "mlp_h2_rescale")
+        _lib.api().mlp_h2_rescale(self.P, self.idx_fb, self.idx_tb, self.PH, self.PTH, self.h2_scales, _lib.stream_ptr())
 
     def _planes_live(self):
         return self._gemm == "bf16x3" or self.gemm_infer == "bf16x3"
@@ -224,11 +223,8 @@ class PackedPolicy:
         mu = torch.empty((n, NACT), device=self.device) if want_mu else None
         v = torch.empty((n,), device=self.device) if want_v else None
         s = saves or {}
-        ptr = lambda t: None if t is None else p(t)   # noqa: E731
-        _lib.check(self._lib.mlp_forward(ptr(self.P), ptr(self.PF), ptr(x2), C.c_int64(n), ptr(mu), ptr(v), ptr(s.get("out")),
-                                         ptr(s.get("h1")), ptr(s.get("h2")), ptr(s.get("h3")),
-                                         self.pb_ptr() if saves else self.infer_pb_ptr(), _lib.stream_ptr()),
-                   "mlp_forward")
+        _lib.api().mlp_forward(self.P, self.PF, x2, n, mu, v, s.get("out"), s.get("h1"), s.get("h2"), s.get("h3"),
+                              self.pb_ptr() if saves else self.infer_pb_ptr(), _lib.stream_ptr())
         return (mu.view(*lead, NACT) if want_mu else None), (v.view(*lead, 1) if want_v else None)
 
     # ---- training on the MFMA kernels (ppo.py:184-199) ------------------------------------------
@@ -325,24 +321,17 @@ class PackedPolicy:
                 self._tile_flags.zero_()
                 self._epoch = 0
             self._epoch += 1
-            _lib.check(self._lib.mlp_forward_backward(
-                p(self.P), p(self.PF), p(self.PT), p(x), C.c_int64(n), p(s["out"]), p(s["h1"]), p(s["h2"]), p(s["h3"]),
-                p(action), p(old_logp), p(adv), p(target), p(var), C.c_float(inv_b), C.c_float(clip),
-                p(d["dz4"]), p(d["dz3"]), p(d["dz2"]), p(d["dz1"]), p(self.loss_part), p(self._tile_flags),
-                C.c_int(self._epoch), p(self.tile_wait_error), self.pb_ptr(), self.ptb_ptr(),
-                C.c_int(1 if self.handoff == "sc1" else 0), st), "mlp_forward_backward")
+            _lib.api().mlp_forward_backward(
+                self.P, self.PF, self.PT, x, n, s["out"], s["h1"], s["h2"], s["h3"], action, old_logp, adv, target, var, inv_b, clip,
+                d["dz4"], d["dz3"], d["dz2"], d["dz1"], self.loss_part, self._tile_flags, self._epoch, self.tile_wait_error,
+                self.pb_ptr(), self.ptb_ptr(), 1 if self.handoff == "sc1" else 0, st)
         else:
-            _lib.check(self._lib.mlp_forward(p(self.P), p(self.PF), p(x), C.c_int64(n), None, None, p(s["out"]), p(s["h1"]),
-                                             p(s["h2"]), p(s["h3"]), self.pb_ptr(), st), "mlp_forward")
-            _lib.check(self._lib.mlp_backward_dx(p(self.PT), p(s["out"]), p(s["h1"]), p(s["h2"]), p(s["h3"]), p(action),
-                                                 p(old_logp), p(adv), p(target), p(var), C.c_int64(n), C.c_float(inv_b),
-                                                 C.c_float(clip), p(d["dz4"]), p(d["dz3"]), p(d["dz2"]), p(d["dz1"]),
-                                                 p(self.loss_part), self.ptb_ptr(), st), "mlp_backward_dx")
-        nm = (p(self.grad_mask), p(self._norm_ws), p(self.step)) if fuse_norm else (None, None, None)
-        _lib.check(self._lib.mlp_grad_w(p(x), p(s["h1"]), p(s["h2"]), p(s["h3"]), p(d["dz1"]), p(d["dz2"]),
-                                        p(d["dz3"]), p(d["dz4"]), C.c_int64(n), p(self.workspace), p(self.G), *nm,
-                                        p(self.tile_wait_error), C.c_int(1 if self.gemm == "bf16x3" else 0), st),
-                   "mlp_grad_w")
+            _lib.api().mlp_forward(self.P, self.PF, x, n, None, None, s["out"], s["h1"], s["h2"], s["h3"], self.pb_ptr(), st)
+            _lib.api().mlp_backward_dx(self.PT, s["out"], s["h1"], s["h2"], s["h3"], action, old_logp, adv, target, var, n, inv_b,
+                                      clip, d["dz4"], d["dz3"], d["dz2"], d["dz1"], self.loss_part, self.ptb_ptr(), st)
+        nm = (self.grad_mask, self._norm_ws, self.step) if fuse_norm else (None, None, None)
+        _lib.api().mlp_grad_w(x, s["h1"], s["h2"], s["h3"], d["dz1"], d["dz2"], d["dz3"], d["dz4"], n, self.workspace, self.G, *nm,
+                             self.tile_wait_error, 1 if self.gemm == "bf16x3" else 0, st)
 
     def _fused_grad(self, x, action, old_logp, adv, target, var, clip, inv_b, fuse_norm, dump):
         """`mlp_fused_grad`: one persistent launch + the slab reduction.  dump=True (tests) also writes the chain's values into
@@ -351,21 +340,19 @@ class PackedPolicy:
         if self._fused_ws is None:
             self._fused_ws = torch.empty(int(max(self._lib.mlp_fused_workspace_floats(), self._lib.mlp_fused_h2_workspace_floats())),
                                          device=self.device)
-        nm = (p(self.grad_mask), p(self._norm_ws), p(self.step)) if fuse_norm else (None, None, None)
+        nm = (self.grad_mask, self._norm_ws, self.step) if fuse_norm else (None, None, None)
         dptr = None
         if dump:
             s, d = self.saves, self.dz
             arr = (C.c_void_p * 8)(*[t.data_ptr() for t in (s["out"], s["h1"], s["h2"], s["h3"], d["dz4"], d["dz3"], d["dz2"], d["dz1"])])
             dptr = arr
         if self.h2_live() and not self.h2_suspended:
-            _lib.check(self._lib.mlp_fused_grad_h2(p(self.P), p(self.PH), p(self.PTH), p(self.h2_scales), p(self.h2_overflow),
-                                                   C.c_int(1 if self.h2_freeze else 0), p(x), C.c_int64(n), p(action), p(old_logp),
-                                                   p(adv), p(target), p(var), C.c_float(inv_b), C.c_float(clip), p(self._fused_ws),
-                                                   p(self.G), *nm, p(self.loss_part), dptr, _lib.stream_ptr()), "mlp_fused_grad_h2")
+            _lib.api().mlp_fused_grad_h2(self.P, self.PH, self.PTH, self.h2_scales, self.h2_overflow, 1 if self.h2_freeze else 0, x, n,
+                                        action, old_logp, adv, target, var, inv_b, clip, self._fused_ws, self.G, *nm, self.loss_part,
+                                        dptr, _lib.stream_ptr())
             return
-        _lib.check(self._lib.mlp_fused_grad(p(self.P), p(self.PB), p(self.PTB), p(x), C.c_int64(n), p(action), p(old_logp), p(adv),
-                                            p(target), p(var), C.c_float(inv_b), C.c_float(clip), p(self._fused_ws), p(self.G), *nm,
-                                            p(self.loss_part), dptr, _lib.stream_ptr()), "mlp_fused_grad")
+        _lib.api().mlp_fused_grad(self.P, self.PB, self.PTB, x, n, action, old_logp, adv, target, var, inv_b, clip, self._fused_ws,
+                                 self.G, *nm, self.loss_part, dptr, _lib.stream_ptr())
 
     def calibrate_h2(self, x, action, old_logp, adv, target, var, clip, global_rows=None, max_launches=12):
         """Bring the activation / gradient scales of the fp16x2 step to the data (host-synchronising; before the first update on a new
@@ -452,12 +439,8 @@ class PackedPolicy:
         step_out = None
         if self_norm:
             self._step_idx ^= 1
-            step_out = p(self.step)
-        _lib.check(self._lib.mlp_adam_step(p(self.P), p(self.PF), p(self.PT), p(self.idx_f), p(self.idx_t), p(self.G),
-                                           p(self.grad_mask), p(self.exp_avg),
-                                           p(self.exp_avg_sq), p(step_in), C.c_float(self.lr),
-                                           C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps),
-                                           C.c_float(self.max_norm), C.c_float(grad_scale), p(self._norm_ws),
-                                           C.c_int(1 if norm_ready else 0), *self._plane_args(), step_out,
-                                           p(grad_invalid) if grad_invalid is not None else None, *self._h2_args(), _lib.stream_ptr()),
-                   "mlp_adam_step")
+            step_out = self.step
+        _lib.api().mlp_adam_step(self.P, self.PF, self.PT, self.idx_f, self.idx_t, self.G, self.grad_mask, self.exp_avg,
+                                self.exp_avg_sq, step_in, self.lr, self.betas[0], self.betas[1], self.eps, self.max_norm, grad_scale,
+                                self._norm_ws, 1 if norm_ready else 0, *self._plane_args(), step_out, grad_invalid,
+                                *self._h2_args(), _lib.stream_ptr())

@@ -33,8 +33,6 @@ from .fly import Fly
 from .params import NUM_DOF
 
 
-p = _lib.ptr
-
 
 class Net(nn.Module):
     """ppo.py:10-102: shared 73-256-128 (ELU); actor 128-64-18 with ELU after BOTH layers;
@@ -349,7 +347,7 @@ class PPO:
         self._obs_norm_ring = torch.empty_like(self._obs_ring)
         self._obs_sets = torch.zeros((_lib.OBS_NORM_SETS, _lib.OBS_NORM_SET), dtype=torch.float64, device=dev)
         torch.cuda.synchronize(dev)                                 # the table is in place before any launch reads it
-        _lib.check(self._lib.fly_set_obs_norm(self.env._handle, C.c_void_p(self._obs_table.data_ptr())), "fly_set_obs_norm")
+        _lib.api().fly_set_obs_norm(self.env._handle, self._obs_table)
 
     @property
     def obs_mean(self):
@@ -371,14 +369,13 @@ class PPO:
         float64 moments of rows 1..T (the observations this rollout produced; row 0 is the previous rollout's row T) into
         _obs_sets.  Idempotent until the next merge."""
         T, n = self.rollout_size, int(self.args.num_envs)
-        _lib.check(self._lib.ppo_obs_norm_pass(p(self._obs_ring), C.c_int64((T + 1) * n), C.c_int64(n), p(self._obs_table),
-                                               p(self._obs_norm_ring), p(self._obs_sets), _lib.stream_ptr()), "ppo_obs_norm_pass")
+        _lib.api().ppo_obs_norm_pass(self._obs_ring, (T + 1) * n, n, self._obs_table, self._obs_norm_ring, self._obs_sets,
+                                    _lib.stream_ptr())
 
     def _merge_obs_stats(self):
         """Fold the moments of the last pass into S (all ranks' sets, in rank order) and rewrite the table: S_k -> S_k+1."""
         sets = self._all_rank_sets(self._obs_sets, "_keep_sets")
-        _lib.check(self._lib.ppo_obs_norm_merge(p(self._obs_stats), p(self._obs_table), p(sets), C.c_int64(sets.shape[0]),
-                                                C.c_float(self.obs_clip), _lib.stream_ptr()), "ppo_obs_norm_merge")
+        _lib.api().ppo_obs_norm_merge(self._obs_stats, self._obs_table, sets, sets.shape[0], self.obs_clip, _lib.stream_ptr())
 
     # ------------------------------------------------------------------------------------------
     # value normalisation (opt-in)
@@ -431,24 +428,20 @@ class PPO:
         is written, so it is idempotent on a finished rollout."""
         T, n = self.rollout_size, int(self.args.num_envs)
         if self.gae == "episodic":
-            _lib.check(self._lib.ppo_td_gae_episodic_vnorm(
-                p(self.all_reward), p(values[:T]), p(values[1:]), p(self._reset_rows), p(self._progress_rows),
-                p(self._ended_prev), C.c_int64(self.env.max_episode_length), p(self._value_table), C.c_float(self.gamma),
-                C.c_float(self.lmbda), C.c_int64(T), C.c_int64(n), p(self._target), p(self.all_advantage), p(self._value_sets),
-                C.c_int(mode), _lib.stream_ptr()), "ppo_td_gae_episodic_vnorm")
+            _lib.api().ppo_td_gae_episodic_vnorm(
+                self.all_reward, values[:T], values[1:], self._reset_rows, self._progress_rows, self._ended_prev,
+                self.env.max_episode_length, self._value_table, self.gamma, self.lmbda, T, n, self._target, self.all_advantage,
+                self._value_sets, mode, _lib.stream_ptr())
         else:
-            _lib.check(self._lib.ppo_td_gae_vnorm(
-                p(self.all_reward), p(values[:T]), p(values[1:]), p(done_f), p(self._value_table), C.c_float(self.gamma),
-                C.c_float(self.lmbda), C.c_int64(T), C.c_int64(n), p(self._target), p(self.all_advantage), p(self._value_sets),
-                C.c_int(mode), _lib.stream_ptr()), "ppo_td_gae_vnorm")
+            _lib.api().ppo_td_gae_vnorm(
+                self.all_reward, values[:T], values[1:], done_f, self._value_table, self.gamma, self.lmbda, T, n, self._target,
+                self.all_advantage, self._value_sets, mode, _lib.stream_ptr())
         if self.lambda_returns:
             self._lambda_targets(values, self._value_table, self._value_sets)      # the targets AND their moments: S_v is theirs
         sets = self._all_rank_sets(self._value_sets, "_keep_value_sets")
-        _lib.check(self._lib.ppo_value_norm_merge(p(self._value_stats), p(sets), C.c_int64(sets.shape[0]),
-                                                  p(self._value_stats_next), p(self._value_table_next), _lib.stream_ptr()),
-                   "ppo_value_norm_merge")
-        _lib.check(self._lib.ppo_value_norm_apply(p(self._target), C.c_int64(T * n), p(self._value_table_next),
-                                                  p(self._target_norm), _lib.stream_ptr()), "ppo_value_norm_apply")
+        _lib.api().ppo_value_norm_merge(self._value_stats, sets, sets.shape[0], self._value_stats_next, self._value_table_next,
+                                       _lib.stream_ptr())
+        _lib.api().ppo_value_norm_apply(self._target, T * n, self._value_table_next, self._target_norm, _lib.stream_ptr())
 
     def _lambda_targets(self, values, table, sets):
         """Opt-in (`lambda_returns`): _target <- all_advantage + v(obs_t) in reward units (ppo_lambda_targets: one launch, no
@@ -456,9 +449,7 @@ class PPO:
         outputs it read.  `table` / `sets` (value normalisation) or None: denormalise v under the committed table, and write
         the float64 moment sets of the new targets over the TD targets'."""
         T, n = self.rollout_size, int(self.args.num_envs)
-        _lib.check(self._lib.ppo_lambda_targets(
-            p(self.all_advantage), p(values[:T]), p(table) if table is not None else None, C.c_int64(T * n), p(self._target),
-            p(sets) if sets is not None else None, _lib.stream_ptr()), "ppo_lambda_targets")
+        _lib.api().ppo_lambda_targets(self.all_advantage, values[:T], table, T * n, self._target, sets, _lib.stream_ptr())
 
     def _commit_value_stats(self):
         """S_v <- scratch, table <- scratch table: the next make_data denormalises under the table this update trained on."""
@@ -486,10 +477,8 @@ class PPO:
         [rows], tests) receives the source rows."""
         T, n = self.rollout_size, int(self.args.num_envs)
         so, sa, sl, st, sv = self._mb_stage
-        _lib.check(self._lib.ppo_minibatch_gather(
-            p(obs), p(action), p(old_log_prob), p(advantage), p(target), C.c_int64(T * n), C.c_uint32(self._mb_seed),
-            C.c_uint32(epoch_key & 0xFFFFFFFF), C.c_int64(first), C.c_int64(rows), p(so), p(sa), p(sl), p(sv), p(st),
-            p(self._mb_index) if self._mb_index is not None else None, _lib.stream_ptr()), "ppo_minibatch_gather")
+        _lib.api().ppo_minibatch_gather(obs, action, old_log_prob, advantage, target, T * n, self._mb_seed, epoch_key & 0xFFFFFFFF,
+                                       first, rows, so, sa, sl, sv, st, self._mb_index, _lib.stream_ptr())
         return so, sa, sl, st, sv
 
     def _minibatches(self):
@@ -537,10 +526,9 @@ class PPO:
     def _td_gae_episodic(self, values, mode):
         """make_data's GAE pass with gae='episodic' (ppo_td_gae_episodic): straight from the int64 flag rows, no conversions."""
         T, n = self.rollout_size, int(self.args.num_envs)
-        _lib.check(self._lib.ppo_td_gae_episodic(
-            p(self.all_reward), p(values[:T]), p(values[1:]), p(self._reset_rows), p(self._progress_rows), p(self._ended_prev),
-            C.c_int64(self.env.max_episode_length), C.c_float(self.gamma), C.c_float(self.lmbda), C.c_int64(T), C.c_int64(n),
-            p(self._target), p(self.all_advantage), C.c_int(mode), _lib.stream_ptr()), "ppo_td_gae_episodic")
+        _lib.api().ppo_td_gae_episodic(
+            self.all_reward, values[:T], values[1:], self._reset_rows, self._progress_rows, self._ended_prev,
+            self.env.max_episode_length, self.gamma, self.lmbda, T, n, self._target, self.all_advantage, mode, _lib.stream_ptr())
 
     # ------------------------------------------------------------------------------------------
     # episode statistics (opt-in)
@@ -563,13 +551,10 @@ class PPO:
         host sync."""
         T, n = self.rollout_size, int(self.args.num_envs)
         mode = 4 if n < 512 and T >= 1024 else 0                    # PPO_GAE_SCAN: make_data's rule
-        _lib.check(self._lib.ppo_episode_stats(
-            p(self.all_reward), p(self._reset_rows), p(self._progress_rows), C.c_int64(self.env.max_episode_length), C.c_int64(T),
-            C.c_int64(n), p(self._ep_carry_ret), p(self._ep_carry_len), p(self._ep_sets), C.c_int(mode), _lib.stream_ptr()),
-            "ppo_episode_stats")
+        _lib.api().ppo_episode_stats(self.all_reward, self._reset_rows, self._progress_rows, self.env.max_episode_length, T, n,
+                                    self._ep_carry_ret, self._ep_carry_len, self._ep_sets, mode, _lib.stream_ptr())
         sets = self._all_rank_sets(self._ep_sets, "_keep_ep_sets")
-        _lib.check(self._lib.ppo_episode_stats_merge(p(sets), C.c_int64(sets.shape[0]), p(self._ep_window), p(self._ep_total),
-                                                     _lib.stream_ptr()), "ppo_episode_stats_merge")
+        _lib.api().ppo_episode_stats_merge(sets, sets.shape[0], self._ep_window, self._ep_total, _lib.stream_ptr())
 
     @staticmethod
     def _episode_suffix(w):
@@ -633,12 +618,9 @@ class PPO:
         if rows <= 0:
             return
         n = int(self.args.num_envs)
-        P = C.c_void_p
-        _lib.check(self._lib.ppo_rollout_bookkeeping(
-            P(self.all_reward[self._book_from].data_ptr()), C.c_int64(rows), C.c_int64(n), P(self._book_terms.data_ptr()),
-            P(self._score_acc.data_ptr()), C.c_float(1.0 / self.num_eval_freq), P(self._action_var.data_ptr()),
-            C.c_int(self.num_acts), C.c_float(self._var_decay), self._var_min, P(self._rows_applied.data_ptr()),
-            _lib.stream_ptr()), "ppo_rollout_bookkeeping")
+        _lib.api().ppo_rollout_bookkeeping(
+            self.all_reward[self._book_from], rows, n, self._book_terms, self._score_acc, 1.0 / self.num_eval_freq,
+            self._action_var, self.num_acts, self._var_decay, self._var_min, self._rows_applied, _lib.stream_ptr())
         self._book_from = self._rows_done
 
     def make_data(self):
@@ -673,10 +655,8 @@ class PPO:
                 if self.normalize_value:
                     self._td_gae_vnorm(values, done_f, mode)        # `values` are normalised-unit outputs: denormalised there
                 else:
-                    _lib.check(self._lib.ppo_td_gae(
-                        p(self.all_reward), p(values[:T]), p(values[1:]), p(done_f), C.c_float(self.gamma),
-                        C.c_float(self.lmbda), C.c_int64(T), C.c_int64(n), p(self._target), p(self.all_advantage),
-                        C.c_int(mode), _lib.stream_ptr()), "ppo_td_gae")
+                    _lib.api().ppo_td_gae(self.all_reward, values[:T], values[1:], done_f, self.gamma, self.lmbda, T, n,
+                                         self._target, self.all_advantage, mode, _lib.stream_ptr())
                 self._keep = (values, done_f)                       # alive until the stream has consumed them
             if self.lambda_returns and not self.normalize_value:
                 self._lambda_targets(values, None, None)            # (with normalize_value: inside _td_gae_vnorm)
@@ -691,16 +671,13 @@ class PPO:
         ALL ranks.  Not in the reference (ppo.py:171 uses raw advantages); named by BASELINE's north_star."""
         import torch.distributed as dist
         cnt = self.all_advantage.numel()
-        _lib.check(self._lib.ppo_adv_stats(p(self.all_advantage), C.c_int64(cnt), p(self._adv_stats), _lib.stream_ptr()),
-                   "ppo_adv_stats")
+        _lib.api().ppo_adv_stats(self.all_advantage, cnt, self._adv_stats, _lib.stream_ptr())
         if self.world_size > 1:
             mine = self._adv_stats[:2].clone()
             parts = [torch.empty_like(mine) for _ in range(self.world_size)]
             dist.all_gather(parts, mine)                            # every rank combines the same pairs in rank order
             self._adv_stats[:2].copy_(combine_adv_stats(torch.stack(parts), cnt))
-        _lib.check(self._lib.ppo_adv_apply(p(self.all_advantage), C.c_int64(cnt), p(self._adv_stats),
-                                           C.c_float(float(cnt * self.world_size)), C.c_float(1e-8), _lib.stream_ptr()),
-                   "ppo_adv_apply")
+        _lib.api().ppo_adv_apply(self.all_advantage, cnt, self._adv_stats, float(cnt * self.world_size), 1e-8, _lib.stream_ptr())
 
     def minibatch_loss(self, obs_mc, action_mc, old_log_prob_mc, target_mc, advantage_mc):
         """ppo.py:184-194.  Old log-prob is of the unclipped sample, the new one of the stored
@@ -1001,9 +978,7 @@ class PPO:
         self._eps_all.normal_(generator=self._gen)
         if self.action_noise == "ar1":
             T, n = self.rollout_size, int(self.args.num_envs)
-            _lib.check(self._lib.ppo_noise_ar1(
-                C.c_void_p(self._eps_all.data_ptr()), C.c_void_p(self._noise_carry.data_ptr()), C.c_int64(T),
-                C.c_int64(n * self.num_acts), C.c_float(self.noise_rho), _lib.stream_ptr()), "ppo_noise_ar1")
+            _lib.api().ppo_noise_ar1(self._eps_all, self._noise_carry, T, n * self.num_acts, self.noise_rho, _lib.stream_ptr())
 
     def _launch_step(self, t):
         """The device work of one env step (ppo.py:213-237): ONE launch (`ppo_rollout_step`), no host logic.  Rows of
@@ -1038,7 +1013,6 @@ class PPO:
     def _launch_rollout(self):
         """The device work of a WHOLE rollout in one launch (`ppo_rollout_all`): eps draw, then every workgroup runs
         the T steps of its own 32 envs with the env state in registers.  Bit for bit what T `_launch_step` calls leave."""
-        P = C.c_void_p
         pol, env, T = self.policy, self.env, self.rollout_size
         self._draw_noise()
         self._rows_applied.zero_()
@@ -1053,15 +1027,13 @@ class PPO:
             # rendered first (none unless a rollout was cut short), then the record is (re)registered
             rec.buffer(T)
             rec.flush()
-            _lib.check(self._lib.fly_set_pose_record(env._handle, P(rec.poses.data_ptr())), "fly_set_pose_record")
+            _lib.api().fly_set_pose_record(env._handle, rec.poses)
         # env._bufs.reset / .progress point at the CURRENT flags (the env's own tensors, or the last row of the previous
         # rollout): the launch reads them once, then writes step t's flags to row t
-        _lib.check(self._lib.ppo_rollout_all(
-            env._handle, C.byref(env._bufs), P(pol.P.data_ptr()), P(pol.PF.data_ptr()), P(self._obs_ring.data_ptr()),
-            P(self._eps_all.data_ptr()), P(self._action_var.data_ptr()), C.c_float(self._var_decay), self._var_min,
-            P(self.all_acts.data_ptr()), P(self.all_log_prob.data_ptr()), P(self._v_ring.data_ptr()),
-            P(self.all_reward.data_ptr()), C.c_int(T), P(self._rows_applied.data_ptr()), pol.infer_pb_ptr(),
-            P(self._reset_rows.data_ptr()), P(self._progress_rows.data_ptr()), _lib.stream_ptr()), "ppo_rollout_all")
+        _lib.api().ppo_rollout_all(
+            env._handle, C.byref(env._bufs), pol.P, pol.PF, self._obs_ring, self._eps_all, self._action_var, self._var_decay,
+            self._var_min, self.all_acts, self.all_log_prob, self._v_ring, self.all_reward, T, self._rows_applied,
+            pol.infer_pb_ptr(), self._reset_rows, self._progress_rows, _lib.stream_ptr())
 
     def _after_step(self, t):
         """Host-side state of a step that has been issued (launched or replayed): rows whose score / variance

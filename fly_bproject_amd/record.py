@@ -45,8 +45,7 @@ def render(fly, poses, rc=None, with_ids=False):
     f = int(poses.shape[0])
     rgba = torch.empty((f, rc.height, rc.width), dtype=torch.int32, device=poses.device)
     ids = torch.empty((f, rc.height, rc.width), dtype=torch.uint8, device=poses.device) if with_ids else None
-    _lib.check(fly._lib.fly_render(fly._handle, C.c_void_p(poses.data_ptr()), f, C.byref(rc), C.c_void_p(rgba.data_ptr()),
-                                   C.c_void_p(ids.data_ptr()) if ids is not None else None, _lib.stream_ptr()), "fly_render")
+    _lib.api().fly_render(fly._handle, poses, f, C.byref(rc), rgba, ids, _lib.stream_ptr())
     return rgba, ids
 
 

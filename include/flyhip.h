@@ -47,6 +47,7 @@
 extern "C" {
 #endif
 
+#define FLY_ABI_VERSION 13   /* what fly_abi_version() returns: bumped whenever an argument list or a structure changes */
 #define FLY_NUM_DOF 18
 #define FLY_NUM_OBS 73
 #define FLY_NUM_LEGS 6

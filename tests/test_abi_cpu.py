@@ -35,6 +35,110 @@ def test_binding_table_matches_header(built):
     built.load()
 
 
+def _bound_structs():
+    """{C structure name: its ctypes binding}."""
+    from fly_bproject_amd import _lib
+    from fly_bproject_amd.params import FlyParams
+    return {"FlyConfig": FlyParams, "FlyBuffers": _lib.FlyBuffers, "FlyRenderConfig": _lib.FlyRenderConfig,
+            "FlyRandomization": _lib.FlyRandomization}
+
+
+def test_binding_rows_match_the_prototypes(built):
+    """Every prototype of include/flyhip.h has a SYMBOLS row with one entry per parameter, of the ctypes type that parameter's
+    C type binds to (tests/abi_header.py), and after load() every function's restype is the declared return type."""
+    from tests import abi_header
+    protos, structs = abi_header.prototypes(), _bound_structs()
+    assert len(protos) == 66 and set(protos) == set(built.SYMBOLS) | {"fly_last_error"}
+    lib = built.load()
+    wrong = {}
+    for name, (ret, params) in protos.items():
+        want = [abi_header.ctype_of(t, structs) for t in params]
+        fn = getattr(lib, name)
+        if list(fn.argtypes) != want or fn.restype is not abi_header.RETURNS[ret]:
+            wrong[name] = (params, fn.argtypes, ret, fn.restype)
+        if name != "fly_last_error" and built.SYMBOLS[name] != want:
+            wrong[name] = (params, built.SYMBOLS[name])
+    assert not wrong, wrong
+
+
+# the FLY_* sizes fly_bproject_amd/_lib.py restates, by the macro each one restates
+_RESTATED_SIZES = {"FLY_POSE_FLOATS": "POSE_FLOATS", "FLY_OBS_NORM_TABLE": "OBS_NORM_SET", "FLY_OBS_NORM_SET": "OBS_NORM_SET",
+                   "FLY_OBS_NORM_SETS": "OBS_NORM_SETS", "FLY_VALUE_NORM_TABLE": "VALUE_NORM_TABLE",
+                   "FLY_VALUE_NORM_SET": "VALUE_NORM_SET", "FLY_VALUE_NORM_SETS": "VALUE_NORM_SETS",
+                   "FLY_EPISODE_SET": "EPISODE_SET", "FLY_EPISODE_SETS": "EPISODE_SETS", "FLY_DR_PARAMS": "DR_PARAMS",
+                   "FLY_DR_ROW": "DR_ROW"}
+
+
+def test_constants_and_structures_match_the_header(tmp_path):
+    """_lib.ABI_VERSION, the FLY_* sizes _lib.py restates, and the size and every field's offset and size of the four ctypes
+    structures equal what a host C++ program that includes include/flyhip.h prints for them.  No compiler is a failure."""
+    from fly_bproject_amd import _lib
+    structs = _bound_structs()
+    exprs = {"FLY_ABI_VERSION": "FLY_ABI_VERSION"}
+    exprs.update({m: m for m in _RESTATED_SIZES})
+    want = {"FLY_ABI_VERSION": _lib.ABI_VERSION}
+    want.update({m: getattr(_lib, py) for m, py in _RESTATED_SIZES.items()})
+    assert len(_RESTATED_SIZES) == 11
+    for cname, S in structs.items():
+        exprs["sizeof.%s" % cname], want["sizeof.%s" % cname] = "sizeof(%s)" % cname, C.sizeof(S)
+        assert len(S._fields_) >= 4
+        for field in (f[0] for f in S._fields_):
+            d = getattr(S, field)
+            exprs["offsetof.%s.%s" % (cname, field)], want["offsetof.%s.%s" % (cname, field)] = "offsetof(%s, %s)" % (cname, field), d.offset
+            exprs["sizeof.%s.%s" % (cname, field)], want["sizeof.%s.%s" % (cname, field)] = "sizeof(%s::%s)" % (cname, field), d.size
+    got = _host_program_values(tmp_path, "abi_layout", ("flyhip.h",), exprs)
+    assert got == want, {n: (got[n], want[n]) for n in got if got[n] != want[n]}
+
+
+def test_api_converts_arguments_as_the_argtypes_say():
+    """The checked binding's marshalling, over CFUNCTYPE callbacks standing in for C functions (no library, no GPU): a tensor
+    arrives as its data_ptr(), None as NULL, a float as its float32 value, an int64 above 2^32 intact, and a byref structure
+    and a c_void_p instance pass through."""
+    import torch
+    from fly_bproject_amd import _lib
+    seen = []
+
+    def stand_in(restype, argtypes, rc=0):
+        def record(*args):
+            seen.append(args)
+            return rc
+        cb = C.CFUNCTYPE(restype, *argtypes)(record)
+        cb.argtypes, cb.restype = list(argtypes), restype
+        return cb
+    P, L, F, I = C.c_void_p, C.c_int64, C.c_float, C.c_int
+    f = _lib._checked("stand_in", stand_in(I, [P, P, L, F, C.POINTER(_lib.FlyBuffers), P, I, P]), lambda: b"stand-in message")
+    t = torch.arange(6, dtype=torch.float32)[2:]                    # a view: its own address, not the storage's
+    bufs = _lib.FlyBuffers()
+    bufs.obs = 0x1234
+    handle = C.c_void_p(0xABCDEF0123)
+    assert f(t, None, (1 << 40) + 5, 0.1, C.byref(bufs), handle, -3, 7 << 33) is None
+    (a_t, a_none, a_l, a_f, a_b, a_h, a_i, a_int_ptr), = seen
+    assert a_t == t.data_ptr() == t.untyped_storage().data_ptr() + 8
+    assert a_none is None                                           # (ctypes hands a NULL void* to a callback as None)
+    assert a_l == (1 << 40) + 5
+    assert a_f == C.c_float(0.1).value != 0.1
+    assert C.addressof(a_b.contents) == C.addressof(bufs) and a_b.contents.obs == 0x1234
+    assert a_h == 0xABCDEF0123 and a_i == -3 and a_int_ptr == 7 << 33
+    # a failing int entry point raises under its own name with the library's message; an int64_t one returns its value
+    g = _lib._checked("stand_in_fails", stand_in(I, [P], rc=-1), lambda: b"stand-in message")
+    with pytest.raises(_lib.FlyHipError, match=r"stand_in_fails failed \(-1\): stand-in message"):
+        g(t)
+    assert _lib._checked("stand_in_floats", stand_in(L, [L], rc=1 << 35), None)(3) == 1 << 35
+    with pytest.raises(TypeError, match="stand_in_fails takes 1 arguments"):
+        g(t, None)
+
+
+def test_api_raises_on_the_librarys_refusals(built):
+    """Through the real library, on refusals that return before any HIP call."""
+    api = built.api()
+    assert api is built.api() and set(vars(api)) == set(built.SYMBOLS)
+    with pytest.raises(built.FlyHipError, match=r"fly_destroy failed .*handle is null"):
+        api.fly_destroy(None)
+    with pytest.raises(built.FlyHipError, match=r"ppo_noise_ar1 failed .*null pointer"):
+        api.ppo_noise_ar1(None, None, 1, 1, 0.5, None)
+    assert api.fly_abi_version() == 13 == built.ABI_VERSION
+
+
 def test_config_struct_layout_matches_oracle():
     """FlyConfig (product) and OrcConfig (oracle) are declared independently; same layout."""
     from fly_bproject_amd.params import FlyParams, default_params
@@ -112,23 +216,30 @@ def _python_layout_values():
     return want
 
 
-def test_python_layout_matches_the_headers(tmp_path):
-    """The numbers fly_bproject_amd/packing.py derives equal the macros of csrc/mlp_layout.h, csrc/dqn_layout.h and the *_ABI
-    sizes of include/flyhip.h, as a host C++ program that includes the three prints them.  No compiler is a failure."""
+def _host_program_values(tmp_path, stem, headers, exprs):
+    """{label: value} of the integer C++ expressions `exprs` ({label: expression}) as a host program that includes `headers`
+    prints them.  No compiler is a failure."""
     import shutil
     import subprocess
-    names = _layout_macros()
-    src = tmp_path / "layout_macros.cpp"
-    src.write_text('#include <cstdio>\n#include "flyhip.h"\n#include "mlp_layout.h"\n#include "dqn_layout.h"\nint main() {\n'
-                   + "".join('    std::printf("%s %%ld\\n", (long)(%s));\n' % (n, n) for n in names) + "    return 0;\n}\n")
+    src = tmp_path / (stem + ".cpp")
+    src.write_text("#include <cstddef>\n#include <cstdio>\n" + "".join('#include "%s"\n' % h for h in headers) + "int main() {\n"
+                   + "".join('    std::printf("%s %%ld\\n", (long)(%s));\n' % (n, e) for n, e in exprs.items()) + "    return 0;\n}\n")
     cxx = shutil.which("g++")
     cmd = [cxx] if cxx else [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-x", "c++"]
-    exe = str(tmp_path / "layout_macros")
+    exe = str(tmp_path / stem)
     subprocess.check_call(cmd + ["-std=c++17", "-I", os.path.join(REPO, "include"), "-I", os.path.join(REPO, "fly_bproject_amd", "csrc"),
                                  str(src), "-o", exe])
     lines = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split("\n")
     got = {n: int(v) for n, v in (line.split() for line in lines if line)}
-    assert set(got) == set(names) and len(got) == len(names)
+    assert set(got) == set(exprs) and len(got) == len(exprs)
+    return got
+
+
+def test_python_layout_matches_the_headers(tmp_path):
+    """The numbers fly_bproject_amd/packing.py derives equal the macros of csrc/mlp_layout.h, csrc/dqn_layout.h and the *_ABI
+    sizes of include/flyhip.h, as a host C++ program that includes the three prints them.  No compiler is a failure."""
+    names = _layout_macros()
+    got = _host_program_values(tmp_path, "layout_macros", ("flyhip.h", "mlp_layout.h", "dqn_layout.h"), {n: n for n in names})
     want = _python_layout_values()
     assert set(got) == set(want), sorted(set(got) ^ set(want))
     assert got == want, {n: (got[n], want[n]) for n in got if got[n] != want[n]}

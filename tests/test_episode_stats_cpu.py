@@ -35,9 +35,6 @@ def test_binding_and_header_agree_and_the_abi_version_stays_13(lib):
     assert ("int ppo_episode_stats(const float* reward, const int64_t* reset, const int64_t* progress, int64_t max_episode_length,\n"
             "                      int64_t T, int64_t N, double* carry_ret, int64_t* carry_len, double* sets, int mode, void* stream);") in header
     assert "int ppo_episode_stats_merge(const double* sets, int64_t nsets, double* window, double* total, void* stream);" in header
-    for name in ("ppo_episode_stats", "ppo_episode_stats_merge"):
-        m = re.search(r"\bint %s\(([^)]*)\);" % name, header)
-        assert m and len(m.group(1).split(",")) == len(_lib.SYMBOLS[name]), name
     macros = dict(re.findall(r"^#define (FLY_EPISODE_SETS?)\s+(\d+)", header, flags=re.M))
     assert (int(macros["FLY_EPISODE_SET"]), int(macros["FLY_EPISODE_SETS"])) == (_lib.EPISODE_SET, _lib.EPISODE_SETS) == (10, 256)
     assert R.SET == _lib.EPISODE_SET

@@ -187,11 +187,7 @@ def test_trainer_flag():
 def test_abi_version_and_new_symbols():
     from fly_bproject_amd import _lib
     assert _lib.ABI_VERSION == 13
-    header = open(os.path.join(REPO, "include", "flyhip.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
     for name in ("ppo_td_gae_episodic", "ppo_td_gae_episodic_vnorm"):
-        assert name in _lib.SYMBOLS, name
-        m = re.search(r"\bint\s+%s\s*\(([^)]*)\)" % name, header)
-        assert m, name
-        assert len(m.group(1).split(",")) == len(_lib.SYMBOLS[name]), name          # one argtype per declared argument
-    assert "return 13;" in open(os.path.join(REPO, "fly_bproject_amd", "csrc", "flyhip_abi.hip")).read()
+        assert name in _lib.SYMBOLS, name                            # (each row is held to the header: tests/test_abi_cpu.py)
+    assert re.search(r"^#define FLY_ABI_VERSION 13\b", open(os.path.join(REPO, "include", "flyhip.h")).read(), flags=re.M)
+    assert "return FLY_ABI_VERSION;" in open(os.path.join(REPO, "fly_bproject_amd", "csrc", "flyhip_abi.hip")).read()

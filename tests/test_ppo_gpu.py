@@ -491,3 +491,23 @@ def test_one_launch_rollout_is_deterministic_run_to_run(n):
         assert torch.isfinite(a.float()).all(), i
         assert torch.equal(a, b), (i, float((a.float() - b.float()).abs().max()))
     assert int(runs[0][5].sum()) > 0                        # episodes ended inside the rollout: the reset path ran too
+
+
+def test_checked_binding_launches_what_the_raw_call_launches():
+    """ppo_td_gae through `_lib.api()` with tensors and plain numbers, and through the raw function with explicit ctypes
+    wrappers: bitwise the same targets and advantages.  T = 3 carries the recurrence, N = 65 leaves a ragged last block."""
+    import ctypes as C
+    from fly_bproject_amd import _lib
+    lib, api, p = _lib.load(), _lib.api(), _lib.ptr
+    T, N = 3, 65
+    g = torch.Generator(device="cuda").manual_seed(11)
+    reward, v, v_next = (torch.randn((T, N), device="cuda", generator=g) for _ in range(3))
+    done = (torch.rand(N, device="cuda", generator=g) > 0.25).float()
+    out = [torch.full((T, N), float("nan"), device="cuda") for _ in range(4)]
+    api.ppo_td_gae(reward, v, v_next, done, 0.99, 0.95, T, N, out[0], out[1], 0, _lib.stream_ptr())
+    _lib.check(lib.ppo_td_gae(p(reward), p(v), p(v_next), p(done), C.c_float(0.99), C.c_float(0.95), C.c_int64(T), C.c_int64(N),
+                              p(out[2]), p(out[3]), C.c_int(0), _lib.stream_ptr()), "ppo_td_gae")
+    torch.cuda.synchronize()
+    assert torch.isfinite(out[0]).all() and torch.isfinite(out[1]).all() and float(out[1].abs().max()) > 0
+    assert torch.equal(out[0].view(torch.int32), out[2].view(torch.int32)), "targets differ"
+    assert torch.equal(out[1].view(torch.int32), out[3].view(torch.int32)), "advantages differ"
