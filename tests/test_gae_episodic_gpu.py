@@ -159,10 +159,11 @@ def assert_every_kind(case):
     assert ((progress >= MAXLEN - 1) & ~ended).any(), "no progress at the limit without the flag"
 
 
-def check_lane(case, tgt, adv, table=None):
-    t32, a32 = E.episodic32(*case, MAXLEN, table)
-    assert np.array_equal(tgt, t32) and np.array_equal(adv, a32)
-    ref = E.episodic64(*case, MAXLEN, G32, GL32, table)
+def check_lane(case, tgt, adv, table=None, maxlen=MAXLEN, where=None):
+    """`where`: a function of the bool [T][N] of the rows that miss -> what the failing assertion says about them."""
+    t32, a32 = E.episodic32(*case, maxlen, table)
+    assert np.array_equal(tgt, t32) and np.array_equal(adv, a32), where((tgt != t32) | (adv != a32)) if where else None
+    ref = E.episodic64(*case, maxlen, G32, GL32, table)
     assert (np.abs(tgt - ref.target) <= 2 * ref.target_err).all()
     assert (np.abs(adv - ref.adv) <= 2 * ref.bound).all()
     return ref
@@ -215,16 +216,18 @@ def scan_case(T, N):
     return (r, v, vn, reset, progress, prev), tuple(ends)
 
 
-def check_scan(case, tgt, adv, table=None):
-    ref = E.episodic64(*case, MAXLEN, G32, GL32, table)
-    t32, _ = E.episodic32(*case, MAXLEN, table)
-    assert np.array_equal(tgt, t32)                          # the targets are elementwise
+def check_scan(case, tgt, adv, table=None, maxlen=MAXLEN, where=None):
+    """`where`: as check_lane's."""
+    ref = E.episodic64(*case, maxlen, G32, GL32, table)
+    t32, _ = E.episodic32(*case, maxlen, table)
+    assert np.array_equal(tgt, t32), where(tgt != t32) if where else None          # the targets are elementwise
     assert (np.abs(tgt - ref.target) <= 2 * ref.target_err).all()
     bound = ref.bound + E.scan_carry_bound64_masked(ref.delta, ref.live, GL32)
     err = np.abs(adv - ref.adv)
     ok = bound > 0
     print("episodic scan T=%d N=%d: max advantage error / bound %.3f" % (adv.shape + (float((err[ok] / bound[ok]).max()),)))
-    assert (err <= SCAN_MARGIN * bound).all()
+    miss = ~(err <= SCAN_MARGIN * bound)
+    assert not miss.any(), where(miss) if where else None
 
 
 @pytest.mark.parametrize("T,N", SCAN_SHAPES)

@@ -223,13 +223,15 @@ SCAN_T = [1, 2, 63, 64, 65, 127, 128, 129, 200, 4097]
 SCAN_MARGIN = 4
 
 
-def check_scan(tag, T, N, mode, tgt, adv, ref):
+def check_scan(tag, T, N, mode, tgt, adv, ref, where=None):
+    """`where`: a function of the bool [T][N] of the rows that miss -> what the failing assertion says about them."""
     check_target(tgt, ref)
     bound = ref.bound + R.scan_carry_bound64(ref.delta, R.gamma_gl32()[1])
     err = np.abs(adv - ref.adv)
     print("%s T=%d N=%d mode=%d: max advantage error / bound %.3f (the carries are up to %.2f of the bound)"
           % (tag, T, N, mode, _ratio(err, bound), float(np.max(1 - ref.bound / bound))))
-    assert (err <= SCAN_MARGIN * bound).all()
+    miss = ~(err <= SCAN_MARGIN * bound)
+    assert not miss.any(), where(miss) if where else None
 
 
 @pytest.mark.parametrize("mode", [0, 1])

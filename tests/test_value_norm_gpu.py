@@ -38,9 +38,19 @@ class _VN:
         self.stats_out = torch.zeros(3, dtype=torch.float64, device=DEV)
         self.table_out = torch.full((4,), -7.0, device=DEV)
 
-    def gae(self, r, v, vn, d, mode):
+    def gae(self, r, v, vn, d, mode, guards=None):
+        """-> (target, adv).  With `guards` = three sentinel-guarded buffers for the targets, the advantages and the sets
+        (objects with .ptr and .get(), as tests/test_gae_episodic_gpu.py's Guarded) the launch writes into those: -> (target,
+        adv, sets [k][3]), the guards checked on the way, and the sets copied to self.sets for merge()."""
         T, N = r.shape
         dr, dv, dvn, dd = cuda(r), cuda(v), cuda(vn), cuda(d)
+        if guards is not None:
+            tgt, adv, sets = guards
+            self._lib.check(self.lib.ppo_td_gae_vnorm(_p(dr), _p(dv), _p(dvn), _p(dd), _p(self.table), 0.99, 0.95, T, N, tgt.ptr,
+                                                      adv.ptr, sets.ptr, mode, None), "ppo_td_gae_vnorm")
+            out = tgt.get().reshape(T, N), adv.get().reshape(T, N), sets.get().reshape(-1, 3)
+            self.sets.copy_(cuda(out[2]))
+            return out
         tgt, adv = torch.empty(T, N, device=DEV), torch.empty(T, N, device=DEV)
         self._lib.check(self.lib.ppo_td_gae_vnorm(_p(dr), _p(dv), _p(dvn), _p(dd), _p(self.table), 0.99, 0.95, T, N, _p(tgt),
                                                   _p(adv), _p(self.sets), mode, None), "ppo_td_gae_vnorm")
