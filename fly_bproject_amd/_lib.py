@@ -1,4 +1,5 @@
-"""ctypes binding of libflyhip.so (include/flyhip.h).  Fails loudly: no library, no product."""
+"""ctypes binding of libflyhip.so (include/flyhip.h, and include/flyhip_ext.h for what was added after its prototype list was
+fixed).  Fails loudly: no library, no product."""
 import ctypes as C
 import os
 
@@ -8,6 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FLYHIP_LIB") or os.path.join(_HERE, "libflyhip.so")
 _lib = None
 _api = None
+_ext = None
 
 
 class FlyHipError(RuntimeError):
@@ -109,6 +111,12 @@ SYMBOLS = {
     "dp_ipc_close": [_P],
     "dp_allreduce_p2p": [_P, _L, C.POINTER(_P), _I, _I, C.c_uint32, _P, _L, _P],
 }
+# include/flyhip_ext.h: the entry points added since flyhip.h's prototype list was fixed -- a table and a binding object of
+# their own (ext()), so that SYMBOLS and api() stay the statement of flyhip.h
+SYMBOLS_EXT = {
+    "ppo_reward_returns": [_P, _P, _F, _L, _L, _P, _P, _P, _I, _P],
+    "ppo_reward_scale": [_P, _L, _P, _F, _P, _P],
+}
 
 
 def build(verbose=False):
@@ -121,7 +129,7 @@ def build(verbose=False):
 
 
 def load():
-    global _lib, _api
+    global _lib, _api, _ext
     if _lib is not None:
         return _lib
     if not os.path.exists(LIB_PATH):
@@ -131,7 +139,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     lib.fly_last_error.restype = C.c_char_p
     lib.fly_last_error.argtypes = []
-    for name, argtypes in SYMBOLS.items():
+    for name, argtypes in list(SYMBOLS.items()) + list(SYMBOLS_EXT.items()):
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.argtypes = argtypes
         fn.restype = C.c_int64 if name.endswith(("_workspace_floats", "_image_halves")) else C.c_int
@@ -141,12 +149,15 @@ def load():
     _api = _Api()
     for name in SYMBOLS:
         setattr(_api, name, _checked(name, getattr(lib, name), lib.fly_last_error))
+    _ext = _Api()
+    for name in SYMBOLS_EXT:
+        setattr(_ext, name, _checked(name, getattr(lib, name), lib.fly_last_error))
     _lib = lib
     return lib
 
 
 class _Api:
-    """One checked callable per SYMBOLS entry (api())."""
+    """One checked callable per SYMBOLS entry (api()), or per SYMBOLS_EXT entry (ext())."""
 
 
 def _checked(name, fn, last_error):
@@ -180,6 +191,13 @@ def api():
     if _api is None:
         load()
     return _api
+
+
+def ext():
+    """api() for the entry points of include/flyhip_ext.h (SYMBOLS_EXT): the same checked callables, on an object of their own."""
+    if _ext is None:
+        load()
+    return _ext
 
 
 def check(rc, what):

@@ -382,6 +382,39 @@ int ppo_episode_stats_merge(const double* sets, int64_t nsets, double* window, d
     return FLY_OK;
 }
 
+int ppo_reward_returns(const float* reward, const int64_t* reset, float gamma, int64_t T, int64_t N, const double* carry_in,
+                       double* carry_out, double* sets, int mode_flags, void* stream)
+{
+    if (!reward || !reset || !carry_in || !carry_out || !sets) return fail(FLY_E_ARG, "ppo_reward_returns: null pointer");
+    if (T < 1 || N < 1) return fail(FLY_E_ARG, "ppo_reward_returns: T and N must be > 0");
+    if (mode_flags != 0 && mode_flags != PPO_GAE_SCAN)
+        return fail(FLY_E_ARG, "ppo_reward_returns: mode_flags must be 0 or PPO_GAE_SCAN (got %d)", mode_flags);
+    if (T > (INT64_MAX >> 3) / N) return fail(FLY_E_ARG, "ppo_reward_returns: T * N int64 rows overflow a byte offset");
+    if (reinterpret_cast<uintptr_t>(reward) & 3) return fail(FLY_E_ARG, "ppo_reward_returns: reward is not 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(reset) | reinterpret_cast<uintptr_t>(carry_in) | reinterpret_cast<uintptr_t>(carry_out) |
+         reinterpret_cast<uintptr_t>(sets)) & 7)
+        return fail(FLY_E_ARG, "ppo_reward_returns: an int64 / float64 buffer is not 8-byte aligned");
+    if (carry_in != carry_out && carry_in < carry_out + N && carry_out < carry_in + N)
+        return fail(FLY_E_ARG, "ppo_reward_returns: carry_out must be carry_in or not overlap it");
+    hipError_t e = flyhip_launch_reward_returns(reward, reset, gamma, T, N, carry_in, carry_out, sets, mode_flags, stream);
+    if (e != hipSuccess) return hip_fail(e, "ppo_reward_returns launch");
+    return FLY_OK;
+}
+
+int ppo_reward_scale(const float* reward, int64_t n, const float* table, float clip, float* out, void* stream)
+{
+    if (!reward || !table || !out) return fail(FLY_E_ARG, "ppo_reward_scale: null pointer");
+    if (n < 1) return fail(FLY_E_ARG, "ppo_reward_scale: n must be > 0");
+    if (!(clip > 0.0f)) return fail(FLY_E_ARG, "ppo_reward_scale: clip must be > 0");
+    if ((reinterpret_cast<uintptr_t>(reward) | reinterpret_cast<uintptr_t>(table) | reinterpret_cast<uintptr_t>(out)) & 3)
+        return fail(FLY_E_ARG, "ppo_reward_scale: a float32 buffer is not 4-byte aligned");
+    if (reward != out && reward < out + n && out < reward + n)
+        return fail(FLY_E_ARG, "ppo_reward_scale: out must be the reward buffer or not overlap it");
+    hipError_t e = flyhip_launch_reward_scale(reward, n, table, clip, out, stream);
+    if (e != hipSuccess) return hip_fail(e, "ppo_reward_scale launch");
+    return FLY_OK;
+}
+
 int ppo_minibatch_gather(const float* obs, const float* act, const float* logp, const float* adv, const float* target, int64_t R,
                          uint32_t seed, uint32_t epoch_key, int64_t first, int64_t n, float* obs_out, float* act_out,
                          float* logp_out, float* adv_out, float* target_out, int32_t* index_out, void* stream)

@@ -71,6 +71,11 @@ hipError_t flyhip_launch_episode_stats(const float* reward, const int64_t* reset
                                        double* sets, int mode, void* stream);
 hipError_t flyhip_launch_episode_stats_merge(const double* sets, int64_t nsets, double* window, double* total, void* stream);
 
+// reward_norm.hip
+hipError_t flyhip_launch_reward_returns(const float* reward, const int64_t* reset, float gamma, int64_t T, int64_t N,
+                                        const double* carry_in, double* carry_out, double* sets, int mode, void* stream);
+hipError_t flyhip_launch_reward_scale(const float* reward, int64_t n, const float* table, float clip, float* out, void* stream);
+
 // minibatch_gather.hip
 hipError_t flyhip_launch_minibatch_gather(const float* obs, const float* act, const float* logp, const float* adv,
                                           const float* target, int64_t R, uint32_t seed, uint32_t epoch_key, int64_t first,

@@ -35,6 +35,15 @@ __device__ __forceinline__ void value_moments_add(double& n, double& mean, doubl
     m2 += d * ((double)x - mean);
 }
 
+// The same update for a value that is a float64 already (reward_norm.hip's discounted returns): not rounded to float first.
+__device__ __forceinline__ void value_moments_add(double& n, double& mean, double& m2, double x)
+{
+    n += 1.0;
+    const double d = x - mean;
+    mean += d / n;
+    m2 += d * (x - mean);
+}
+
 // (n, mean, M2) <- (n, mean, M2) + (nb, mb, qb): Chan et al.'s parallel update; an empty side leaves the other as it is.
 __device__ __forceinline__ void value_moments_merge(double& n, double& mean, double& m2, double nb, double mb, double qb)
 {

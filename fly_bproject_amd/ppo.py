@@ -69,6 +69,7 @@ def diag_gauss_logprob(mu, action, var):
 
 OBS_RMS_KEYS = ("obs_rms.mean", "obs_rms.var", "obs_rms.count")
 VALUE_RMS_KEYS = ("value_rms.mean", "value_rms.var", "value_rms.count")
+REWARD_RMS_KEYS = ("reward_rms.mean", "reward_rms.var", "reward_rms.count")
 
 
 def _split_rms(state_dict, keys, on, what, flag):
@@ -94,6 +95,12 @@ def split_value_rms(state_dict, normalize_value):
     """The value statistics (value_rms.*) out of a loaded state dict.  Without `normalize_value` they are an error: the critic
     was trained on normalised targets, its outputs are not in reward units."""
     return _split_rms(state_dict, VALUE_RMS_KEYS, normalize_value, "value", "normalize_value")
+
+
+def split_reward_rms(state_dict, normalize_reward):
+    """The return statistics (reward_rms.*) out of a loaded state dict.  Without `normalize_reward` they are an error: the
+    critic was trained on scaled rewards, its outputs are not in reward units."""
+    return _split_rms(state_dict, REWARD_RMS_KEYS, normalize_reward, "reward", "normalize_reward")
 
 
 def value_norm_table(stats):
@@ -149,6 +156,7 @@ class PPO:
             self._resume_state = train_state.read_state_file(self.training_state_path(opts.resume_path, opts.rank))
             train_state.check_meta(self._resume_state.get("meta"), args)
             train_state.check_meta_ext(self._resume_state.get("meta_ext"), args)
+            train_state.check_reward_norm(self._resume_state, opts.normalize_reward)
         self.env = env if env is not None else Fly(args)           # ppo.py:110
         self.num_acts = self.env.num_act
         self.num_obs = self.env.num_obs
@@ -221,6 +229,10 @@ class PPO:
         self._episode_stats = opts.episode_stats
         if self._episode_stats:
             self._setup_episode_stats()
+        # opt-in (`normalize_reward`, gymnasium's NormalizeReward / SB3's norm_reward): the GAE pass reads the rewards divided by
+        # the running standard deviation of the discounted return, clamped to +-reward_clip.  all_reward keeps
+        # the raw rows: score line, episode statistics and recorder read what they always did.  See _setup_reward_norm.
+        self.normalize_reward, self.reward_clip = opts.normalize_reward, opts.reward_clip
         # opt-in (`minibatch="shuffled"`): every epoch draws its 15 minibatches from a fresh keyed permutation of ALL T * N rows
         # of the rollout, gathered into one staging set in front of the unchanged optimizer-step kernels.  NOT
         # the reference's contiguous-in-time slices (Q3).  Nothing of it goes into the weights file; `--save_state` carries it
@@ -260,13 +272,14 @@ class PPO:
         self.optim_step = 0
 
         self.net = Net(self.env.num_obs, self.env.num_act).to(dev)
-        loaded_rms, loaded_value_rms = {}, {}
+        loaded_rms, loaded_value_rms, loaded_reward_rms = {}, {}, {}
         if opts.resume or opts.load:                                # ppo.py:147-149; a resumed run's weights file goes in alike
             said, path = ("resuming from: ", opts.resume_path) if opts.resume else ("loaded from: ", self.args.load_path)
             print(said, str(path))
             sd = torch.load(path, map_location=dev, weights_only=True)
             loaded_rms = split_obs_rms(sd, self.normalize_obs)
             loaded_value_rms = split_value_rms(sd, self.normalize_value)
+            loaded_reward_rms = split_reward_rms(sd, self.normalize_reward)
             self.net.load_state_dict(sd)
         self._loaded = opts.load
         from .policy import PackedPolicy
@@ -292,6 +305,8 @@ class PPO:
             self._setup_obs_norm(loaded_rms)
         if self.normalize_value:
             self._setup_value_norm(loaded_value_rms)
+        if self.normalize_reward:
+            self._setup_reward_norm(loaded_reward_rms)
         self._gen = torch.Generator(device=dev)
         self._gen.manual_seed(opts.seed + 1000003 * opts.rank)
         self.world_size = opts.world_size
@@ -419,22 +434,22 @@ class PPO:
             return v
         return v * self._value_table[1] + self._value_table[0]
 
-    def _td_gae_vnorm(self, values, done_f, mode):
+    def _td_gae_vnorm(self, reward, values, done_f, mode):
         """make_data's GAE pass with value normalisation: raw targets and advantages under the COMMITTED table plus the targets'
         moments (ppo_td_gae_vnorm; with gae='episodic' ppo_td_gae_episodic_vnorm, which reads the flag rows, not `done_f`), S_v
         with them folded in and its table into the scratch pair (ppo_value_norm_merge; all ranks' sets in rank order), and the
         targets normalised under the scratch table (ppo_value_norm_apply).  With `lambda_returns` the targets and their moments
         are overwritten by the lambda-returns' right behind the GAE kernel, so everything after it is theirs.  Nothing committed
-        is written, so it is idempotent on a finished rollout."""
+        is written, so it is idempotent on a finished rollout.  `reward` is all_reward, or its scaled copy (normalize_reward)."""
         T, n = self.rollout_size, int(self.args.num_envs)
         if self.gae == "episodic":
             _lib.api().ppo_td_gae_episodic_vnorm(
-                self.all_reward, values[:T], values[1:], self._reset_rows, self._progress_rows, self._ended_prev,
+                reward, values[:T], values[1:], self._reset_rows, self._progress_rows, self._ended_prev,
                 self.env.max_episode_length, self._value_table, self.gamma, self.lmbda, T, n, self._target, self.all_advantage,
                 self._value_sets, mode, _lib.stream_ptr())
         else:
             _lib.api().ppo_td_gae_vnorm(
-                self.all_reward, values[:T], values[1:], done_f, self._value_table, self.gamma, self.lmbda, T, n, self._target,
+                reward, values[:T], values[1:], done_f, self._value_table, self.gamma, self.lmbda, T, n, self._target,
                 self.all_advantage, self._value_sets, mode, _lib.stream_ptr())
         if self.lambda_returns:
             self._lambda_targets(values, self._value_table, self._value_sets)      # the targets AND their moments: S_v is theirs
@@ -455,6 +470,69 @@ class PPO:
         """S_v <- scratch, table <- scratch table: the next make_data denormalises under the table this update trained on."""
         self._value_stats.copy_(self._value_stats_next)
         self._value_table.copy_(self._value_table_next)
+
+    # ------------------------------------------------------------------------------------------
+    # reward scaling (opt-in)
+    def _setup_reward_norm(self, loaded_rms):
+        """The running statistics S_r of the discounted returns (f64: count | mean | var, initially 0 | 0 | 1; the mean is
+        tracked, only the variance scales), their table (f32: m | s | r | 0) and the per-env carries G (f64 [N], the discounted
+        return of each env's open episode): the COMMITTED set, as the last update left it.  Beside it the scratch set that
+        make_data's pass writes (S_r with this rollout's returns folded in, its table, the carries at the rollout's end), the
+        launch's moment sets and the scaled copy of the rewards the GAE launches read.  update() commits scratch -> committed
+        by device copies into these fixed addresses."""
+        dev, T, n = self.device, self.rollout_size, int(self.args.num_envs)
+        self._flag_rows()
+        self._rnorm_stats = torch.tensor([0.0, 0.0, 1.0], dtype=torch.float64, device=dev)
+        if loaded_rms:
+            for i, k in enumerate(("reward_rms.count", "reward_rms.mean", "reward_rms.var")):
+                self._rnorm_stats[i] = loaded_rms[k].to(dev, torch.float64).reshape(())
+        else:
+            self._say_no_statistics("normalize_reward", "return statistics (reward_rms.*)")
+        self._rnorm_table = value_norm_table(self._rnorm_stats).contiguous()
+        self._rnorm_stats_next = self._rnorm_stats.clone()
+        self._rnorm_table_next = self._rnorm_table.clone()
+        self._rnorm_carry = torch.zeros(n, dtype=torch.float64, device=dev)
+        self._rnorm_carry_next = torch.zeros(n, dtype=torch.float64, device=dev)
+        self._rnorm_sets = torch.zeros((_lib.VALUE_NORM_SETS, _lib.VALUE_NORM_SET), dtype=torch.float64, device=dev)
+        self._rnorm_scaled = torch.zeros((T, n, 1), device=dev)
+
+    @property
+    def reward_var(self):
+        """Running population variance of the discounted returns (f64 scalar, a copy), or None when reward scaling is off."""
+        return self._rnorm_stats[2].clone() if self.normalize_reward else None
+
+    @property
+    def reward_count(self):
+        """Returns the running statistics are taken over (f64 scalar, a copy), or None when reward scaling is off."""
+        return self._rnorm_stats[0].clone() if self.normalize_reward else None
+
+    @property
+    def reward_scale(self):
+        """The committed factor r = (float)(1 / sqrt(var + 1e-5)) (f32 scalar, a copy), or None when reward scaling is off."""
+        return self._rnorm_table[2].clone() if self.normalize_reward else None
+
+    def _reward_norm_pass(self):
+        """make_data's first pass with reward scaling: the finished rollout's discounted returns from the COMMITTED carries,
+        their moments and the carries at its end (ppo_reward_returns), S_r with the moments folded in and its table into the
+        scratch pair (ppo_value_norm_merge; all ranks' sets in rank order), and the rewards scaled under the scratch table
+        (ppo_reward_scale): update, then normalise, gymnasium's and SB3's order.  Nothing committed is written, so it is
+        idempotent on a finished rollout.  Returns the buffer the GAE launch reads in place of all_reward."""
+        T, n = self.rollout_size, int(self.args.num_envs)
+        mode = 4 if n < 512 and T >= 1024 else 0                    # PPO_GAE_SCAN: make_data's rule
+        _lib.ext().ppo_reward_returns(self.all_reward, self._reset_rows, self.gamma, T, n, self._rnorm_carry,
+                                     self._rnorm_carry_next, self._rnorm_sets, mode, _lib.stream_ptr())
+        sets = self._all_rank_sets(self._rnorm_sets, "_keep_rnorm_sets")
+        _lib.api().ppo_value_norm_merge(self._rnorm_stats, sets, sets.shape[0], self._rnorm_stats_next, self._rnorm_table_next,
+                                       _lib.stream_ptr())
+        _lib.ext().ppo_reward_scale(self.all_reward, T * n, self._rnorm_table_next, self.reward_clip, self._rnorm_scaled,
+                                   _lib.stream_ptr())
+        return self._rnorm_scaled
+
+    def _commit_rnorm_stats(self):
+        """S_r, table and carries <- scratch: the next rollout's returns go on from where this one's ended."""
+        self._rnorm_stats.copy_(self._rnorm_stats_next)
+        self._rnorm_table.copy_(self._rnorm_table_next)
+        self._rnorm_carry.copy_(self._rnorm_carry_next)
 
     # ------------------------------------------------------------------------------------------
     # shuffled minibatches (opt-in)
@@ -523,11 +601,11 @@ class PPO:
             self._reset_rows = torch.zeros((T, n), dtype=torch.long, device=self.device)
             self._progress_rows = torch.zeros((T, n), dtype=torch.long, device=self.device)
 
-    def _td_gae_episodic(self, values, mode):
+    def _td_gae_episodic(self, reward, values, mode):
         """make_data's GAE pass with gae='episodic' (ppo_td_gae_episodic): straight from the int64 flag rows, no conversions."""
         T, n = self.rollout_size, int(self.args.num_envs)
         _lib.api().ppo_td_gae_episodic(
-            self.all_reward, values[:T], values[1:], self._reset_rows, self._progress_rows, self._ended_prev,
+            reward, values[:T], values[1:], self._reset_rows, self._progress_rows, self._ended_prev,
             self.env.max_episode_length, self.gamma, self.lmbda, T, n, self._target, self.all_advantage, mode, _lib.stream_ptr())
 
     # ------------------------------------------------------------------------------------------
@@ -630,6 +708,7 @@ class PPO:
         v(obs_t) instead of the TD target; the advantages are the same either way."""
         T, n = self.rollout_size, self.args.num_envs
         with torch.no_grad():
+            reward = self._reward_norm_pass() if self.normalize_reward else self.all_reward
             ring = self._obs_ring
             if self.normalize_obs:
                 self._obs_norm_pass()                               # the rows the rollout's policy saw, under the same table
@@ -643,9 +722,9 @@ class PPO:
             mode = 4 if n < 512 and T >= 1024 else 0                # PPO_GAE_SCAN: few envs x long rollout
             if self.gae == "episodic":
                 if self.normalize_value:
-                    self._td_gae_vnorm(values, None, mode)
+                    self._td_gae_vnorm(reward, values, None, mode)
                 else:
-                    self._td_gae_episodic(values, mode)
+                    self._td_gae_episodic(reward, values, mode)
                 self._keep = (values,)
             else:
                 done = self.all_done
@@ -653,9 +732,9 @@ class PPO:
                     mode |= 1                                       # per-step mask; the reference path is [N,1]
                 done_f = done.to(torch.float32).contiguous()
                 if self.normalize_value:
-                    self._td_gae_vnorm(values, done_f, mode)        # `values` are normalised-unit outputs: denormalised there
+                    self._td_gae_vnorm(reward, values, done_f, mode)        # `values` are normalised-unit outputs: denormalised there
                 else:
-                    _lib.api().ppo_td_gae(self.all_reward, values[:T], values[1:], done_f, self.gamma, self.lmbda, T, n,
+                    _lib.api().ppo_td_gae(reward, values[:T], values[1:], done_f, self.gamma, self.lmbda, T, n,
                                          self._target, self.all_advantage, mode, _lib.stream_ptr())
                 self._keep = (values, done_f)                       # alive until the stream has consumed them
             if self.lambda_returns and not self.normalize_value:
@@ -707,6 +786,8 @@ class PPO:
             self._merge_obs_stats()                                 # after update k: the statistics of rollout k + 1
         if self.normalize_value:
             self._commit_value_stats()                              # after update k: the table make_data k + 1 denormalises with
+        if self.normalize_reward:
+            self._commit_rnorm_stats()                             # after update k: S_r and the carries rollout k + 1 goes on from
 
     def _update_torch(self, obs, action, old_log_prob, target, advantage):
         data = (obs, action, old_log_prob, target, advantage)
@@ -1001,7 +1082,7 @@ class PPO:
             rc |= lib.fly_step(env._handle, C.c_void_p(self._act_rows[t].data_ptr()), C.byref(env._bufs), st)  # ppo.py:223
         if rc:
             _lib.check(rc, "rollout step")
-        if self.gae == "episodic" or self._episode_stats:
+        if self.gae == "episodic" or self._episode_stats or self.normalize_reward:
             # row t of the flag rows, as the one-launch rollout writes them itself (captured with the step in a graph)
             self._reset_rows[t].copy_(env.reset_buf)
             self._progress_rows[t].copy_(env.progress_buf)
@@ -1238,6 +1319,9 @@ class PPO:
                 sd["obs_rms.mean"], sd["obs_rms.var"], sd["obs_rms.count"] = self.obs_mean, self.obs_var, self.obs_count
             if self.normalize_value:
                 sd["value_rms.mean"], sd["value_rms.var"], sd["value_rms.count"] = self.value_mean, self.value_var, self.value_count
+            if self.normalize_reward:
+                sd["reward_rms.mean"], sd["reward_rms.var"], sd["reward_rms.count"] = (
+                    self._rnorm_stats[1].clone(), self.reward_var, self.reward_count)
             torch.save(sd, path)
         if not getattr(self.args, "save_state", False):
             return
@@ -1297,6 +1381,8 @@ class PPO:
         if self.normalize_value:
             for k in ("value_stats", "value_table", "value_stats_next", "value_table_next"):
                 agent[k] = pack(getattr(self, "_" + k))
+        if self.normalize_reward:
+            agent["reward_norm"] = {k: pack(getattr(self, "_rnorm_" + k)) for k in train_state.REWARD_NORM_KEYS}
         if self._episode_stats:
             agent["episode_stats"] = {k: pack(getattr(self, "_ep_" + k)) for k in ("carry_ret", "carry_len", "window", "total")}
         state = {"format": train_state.FORMAT, "meta": self._training_state_meta(),
@@ -1327,13 +1413,16 @@ class PPO:
             raise ValueError("load_training_state: update_backend=%r is not part of a training state" % (self.update_backend,))
         train_state.compare_meta(state.get("meta"), self._training_state_meta())
         train_state.check_meta_ext(state.get("meta_ext"), self.args)
+        train_state.check_reward_norm(state, self.normalize_reward)
         agent = train_state.block(state, "agent")
         restore, value = train_state.restore, train_state.value
-        for mine, key, on in ((getattr(self, "_obs_stats", None), "obs_stats", self.normalize_obs),
-                              (getattr(self, "_value_stats", None), "value_stats", self.normalize_value)):
-            if on and torch.is_tensor(agent.get(key)) and not torch.equal(mine.cpu(), agent[key]):
+        for mine, blk, key, on in ((getattr(self, "_obs_stats", None), agent, "obs_stats", self.normalize_obs),
+                                   (getattr(self, "_value_stats", None), agent, "value_stats", self.normalize_value),
+                                   (getattr(self, "_rnorm_stats", None), agent.get("reward_norm"), "stats", self.normalize_reward)):
+            if on and torch.is_tensor(blk.get(key)) and not torch.equal(mine.cpu(), blk[key]):
+                what = key if blk is agent else "reward_norm." + key
                 raise ValueError("training state: %s of the weights file %s and of the state file disagree; they are not of the same "
-                                 "save" % (key, mine.cpu().tolist()[:3]))
+                                 "save" % (what, mine.cpu().tolist()[:3]))
         self._check_step_counter()
         self.flush_log()
         self.policy.load_training_state(train_state.block(state, "policy"))
@@ -1360,6 +1449,9 @@ class PPO:
         if self.normalize_value:
             for k in ("value_stats", "value_table", "value_stats_next", "value_table_next"):
                 restore(getattr(self, "_" + k), agent, "agent", k)
+        if self.normalize_reward:
+            for k in train_state.REWARD_NORM_KEYS:
+                restore(getattr(self, "_rnorm_" + k), agent["reward_norm"], "agent.reward_norm", k)
         if self._episode_stats:
             if isinstance(agent.get("episode_stats"), dict):
                 for k in ("carry_ret", "carry_len", "window", "total"):

@@ -88,6 +88,25 @@ def check_meta_ext(file_ext, args):
                              "options it was saved with (--load_path takes the weights alone)" % (field, held, run_ext[field]))
 
 
+REWARD_NORM_KEYS = ("stats", "table", "stats_next", "table_next", "carry", "carry_next")
+
+
+def check_reward_norm(state, normalize_reward):
+    """`normalize_reward` is named by neither meta block (their fields are fixed), so the PRESENCE of agent["reward_norm"] says
+    whether the state was saved under it: a state with the block resumes only under the flag -- its critic is in scaled
+    units -- and one without it only without the flag.  ValueError otherwise."""
+    agent = state.get("agent") if isinstance(state, dict) else None
+    has = isinstance(agent, dict) and "reward_norm" in agent
+    if has and not isinstance(agent["reward_norm"], dict):
+        raise ValueError("training state: agent.reward_norm is no block")
+    if has and not normalize_reward:
+        raise ValueError("training state: it was saved with normalize_reward (it holds agent.reward_norm); this run is "
+                         "without it: run with --normalize_reward")
+    if normalize_reward and not has:
+        raise ValueError("training state: it was saved without normalize_reward (it holds no agent.reward_norm); this run is "
+                         "with it: run without --normalize_reward")
+
+
 def check_format(state):
     """ValueError unless `state` is a state dict of a format this build reads."""
     if not isinstance(state, dict) or "format" not in state:

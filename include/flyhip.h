@@ -810,4 +810,8 @@ int dp_allreduce_p2p(float* grad, int64_t n_floats, void* const* windows, int32_
 #ifdef __cplusplus
 }
 #endif
+
+/* entry points added since this file's prototype list was fixed (running reward scaling): declared in a file of their own */
+#include "flyhip_ext.h"
+
 #endif /* FLYHIP_H */

@@ -24,6 +24,10 @@ carries ` | Episodes n | Return mean [min, max] | Length mean | Timeouts pct%` o
 score line, every step of an episode counted, the one that performs the reset too.  It observes and steers nothing: weights
 and rollouts are the same bits with and without it.  `--save_state` carries the open episodes and the totals, and a state
 saved with or without the flag resumes with or without it.
+`--normalize_reward` (the GAE pass reads rewards divided by the running standard deviation of the discounted return, DESIGN.md
+3.3i; off by default) with `--reward_clip` (the bound of a scaled reward, default 10.0).  Score line, `--episode_stats` and the
+recorder keep the raw rewards.  The statistics are saved with the checkpoint as reward_rms.* and loaded with it; such a
+checkpoint needs `--normalize_reward` to load, and a `--save_state` state resumes only under the flag it was saved with.
 `--gae episodic` (episode-aware advantage estimate with time-limit bootstrapping; the default `reference` is
 the reference's estimator with its quirks).
 `--minibatch shuffled` (every epoch draws its 15 minibatches from a fresh permutation of ALL rows of the rollout, DESIGN.md
@@ -128,6 +132,12 @@ def parse_args(argv=None):
               'episodes that finished since the previous score line (every step of an episode counts, the one that '
               'performs the reset too: rl_games current_rewards); one kernel over the reward and flag rows at the end of a '
               'rollout, no host sync; changes nothing the rollout or the update reads (DESIGN.md 3.3h); off by default')
+    flag('normalize_reward', action='store_true',
+         help='the GAE pass reads rewards divided by the running standard deviation of the discounted return, clamped to '
+              '+-reward_clip (gymnasium NormalizeReward, SB3 VecNormalize(norm_reward=True); no mean-centring).  The score '
+              'line, --episode_stats and the recorder keep the raw rewards; the critic then lives in scaled units, so the '
+              'statistics are saved with the checkpoint as reward_rms.* (DESIGN.md 3.3i; not in the reference; off by default)')
+    flag('reward_clip', type=float, help='bound of a scaled reward under --normalize_reward, > 0')
     flag('gae', type=str,
          help='advantage estimator: reference = ppo.py:157-171 as it stands (the done mask of the last step over the '
               'whole rollout, no reset of the recurrence at episode ends); episodic = per-step end flags, the '
