@@ -112,7 +112,8 @@ def _beyond(G, want, eff, tensors=range(6), most=16):
     got = _views(G)
     scale = [float(want[t].abs().max()) for t in tensors]
     R = torch.cat([((got[t].double() - want[t]) / sc).reshape(-1) for t, sc in zip(tensors, scale)])
-    D = torch.cat([(eff[t] / sc).reshape(eff[t].shape[0], -1) for t, sc in zip(tensors, scale)], 1)
+    # (an explicit width: a batch with NO ambiguous pair has eff of zero rows, which reshape(0, -1) cannot size)
+    D = torch.cat([(eff[t] / sc).reshape(eff[t].shape[0], want[t].numel()) for t, sc in zip(tensors, scale)], 1)
     taken = []
     cur = float(R.abs().max())
     while D.shape[0] and len(taken) < most:
