@@ -23,6 +23,7 @@
 #include <stdint.h>
 #include "flyhip.h"
 #include "value_norm.h"
+#include "time_scan.h"
 #include "launch.h"
 
 namespace {
@@ -106,9 +107,8 @@ __global__ __launch_bounds__(GAE_BLOCK) void gae_episodic_scan_kernel(EPISODIC_I
     float tm = 0.0f, ts = 1.0f;
     if (VNORM) { tm = table[0]; ts = table[1]; }
     const int lane = threadIdx.x;
-    const long L = (T + 63) / 64;
-    const long t_hi = T - (long)lane * L;                 // exclusive
-    const long t_lo = (t_hi - L > 0) ? t_hi - L : 0;
+    const TimeChunk c = reverse_chunk(T, lane);
+    const long t_lo = c.t_lo, t_hi = c.t_hi;
     double cn = 0.0, cm = 0.0, cq = 0.0;
     for (long e = blockIdx.x; e < N; e += gridDim.x) {
         const bool ended_hi = t_hi > 0 ? reset[(t_hi - 1) * N + e] != 0 : false;
@@ -125,17 +125,8 @@ __global__ __launch_bounds__(GAE_BLOCK) void gae_episodic_scan_kernel(EPISODIC_I
             ended = stale;
         }
         if (t_hi <= 0) { S = 0.0f; m = 1.0f; }
-        // inclusive scan over lanes:  X_l = S_l + m_l * X_{l-1}
-        float sm = m, sv = S;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const float pm = __shfl_up(sm, o, 64), pv = __shfl_up(sv, o, 64);
-            if (lane >= o) { sv = sv + sm * pv; sm = sm * pm; }
-        }
-        float carry = __shfl_up(sv, 1, 64);               // advantage entering this chunk
-        if (lane == 0) carry = 0.0f;
-        // pass 2: the real recurrence from the true carry
-        float a = carry;
+        // pass 2: the real recurrence from the true carry, the advantage entering this chunk
+        float a = affine_carry(m, S, lane);
         ended = ended_hi;
         for (long t = t_hi - 1; t >= t_lo && t_hi > 0; --t) {
             const long i = t * N + e;

@@ -124,14 +124,12 @@ __global__ __launch_bounds__(128) void obs_norm_merge_kernel(double* __restrict_
 extern "C" hipError_t flyhip_launch_obs_norm_pass(const float* ring, int64_t rows, int64_t count_from, const float* table,
                                                   float* out, double* sets, void* stream)
 {
-    hipLaunchKernelGGL(obs_norm_pass_kernel, dim3(FLY_OBS_NORM_SETS), dim3(PASS_THREADS), 0, (hipStream_t)stream, ring, (long)rows,
-                       (long)count_from, table, out, sets);
-    return hipGetLastError();
+    return launch_kernel<obs_norm_pass_kernel>(FLY_OBS_NORM_SETS, PASS_THREADS, 0, stream, ring, (long)rows, (long)count_from, table,
+                                               out, sets);
 }
 
 extern "C" hipError_t flyhip_launch_obs_norm_merge(double* stats, float* table, const double* sets, int64_t k, float clip,
                                                    void* stream)
 {
-    hipLaunchKernelGGL(obs_norm_merge_kernel, dim3(1), dim3(128), 0, (hipStream_t)stream, stats, table, sets, (long)k, clip);
-    return hipGetLastError();
+    return launch_kernel<obs_norm_merge_kernel>(1, 128, 0, stream, stats, table, sets, (long)k, clip);
 }

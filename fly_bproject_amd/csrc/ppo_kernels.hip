@@ -1,9 +1,17 @@
 // ppo_kernels.hip — gfx950 kernels for the PPO rollout math around the policy network.
 //
 //   ppo_sample_logprob_kernel   ppo.py:213-220  a = mu + sqrt(var) eps; log N(a; mu, diag var); clip
-//   ppo_td_gae_kernel           ppo.py:157-171  TD target + delta + reverse GAE recurrence
+//   ppo_td_gae_kernel           ppo.py:157-171  TD target + delta + reverse GAE recurrence, lane = env
+//   ppo_td_gae_scan_kernel                      the same as a wave scan: one wave per env, time on lanes (PPO_GAE_SCAN)
+//   ppo_td_gae_vnorm_kernel                     both with v / v_next mapped to reward units under the value-normalisation table,
+//   ppo_td_gae_vnorm_scan_kernel                plus the float64 moments (count, mean, M2) of the TD targets, one set per workgroup
+//   ppo_adv_stats / _totals / _apply_kernel     advantage normalisation (opt-in)
+//   ppo_bookkeeping_kernel, ppo_row_terms_kernel + ppo_rows_apply_kernel   the score and the action variance's decay
 //
-// Both are streaming kernels (HBM-bound by construction): rows of the row-major [n][18] operands
+// The four GAE kernels are grid mappings around one row (td_gae_row), one backward walk (td_gae_walk) and one scan
+// (td_gae_scan_env): what they compute alike is written once.
+//
+// All are streaming kernels (HBM-bound by construction): rows of the row-major [n][18] operands
 // are staged through LDS so that global traffic is 16-byte coalesced while each lane walks its
 // own row; the [T][N] rollout tensors are walked with lane = env, so every time step is one
 // coalesced 256-byte line per wave and the recurrence lives in a register.
@@ -11,6 +19,7 @@
 #include <stdint.h>
 #include "flyhip.h"
 #include "value_norm.h"
+#include "time_scan.h"
 #include "launch.h"
 
 namespace {
@@ -63,8 +72,71 @@ __global__ __launch_bounds__(SL_BLOCK) void ppo_sample_logprob_kernel(
     }
 }
 
-// lane = env; t walks backwards; loads of step t-1.. are independent of the carried advantage,
-// so the unrolled body keeps several time steps of loads in flight.
+// The reference's row (ppo.py:157-171), written once for the four kernels below.  `a_next` is the advantage carried from t + 1;
+// returns the advantage of this row and its target in `tg`.  VNORM: v / v_next are mapped to reward units under the
+// value-normalisation table first (value_norm.h); otherwise the ops and their order are the same.  All separately rounded.
+template <int MODE, bool VNORM>
+__device__ __forceinline__ float td_gae_row(float r, float v, float v_next, float d, float tm, float ts, float gamma, float gl,
+                                            float a_next, float& tg)
+{
+    const float vv = VNORM ? value_denorm(v, tm, ts) : v;
+    const float vn = VNORM ? value_denorm(v_next, tm, ts) : v_next;
+    tg = __fadd_rn(r, __fmul_rn(__fmul_rn(gamma, vn), d));                            // ppo.py:160
+    const float delta = __fsub_rn(tg, vv);                                            // ppo.py:161
+    const float carry = (MODE & PPO_GAE_MASK_RECURRENCE) ? __fmul_rn(a_next, d) : a_next;
+    return __fadd_rn(__fmul_rn(gl, carry), delta);                                    // ppo.py:167
+}
+
+// the kernels' inputs: the rollout tensors [T][N], `done` per env or per step (MODE), the table's m | s (read under VNORM only)
+#define TD_GAE_INPUTS                                                                                                         \
+    const float* __restrict__ reward, const float* __restrict__ v, const float* __restrict__ v_next,                         \
+        const float* __restrict__ done, float tm, float ts, float gamma, float gl, long N
+
+// Env e's rows t_hi - 1 .. t_lo, backwards from the carried advantage `a`; returns the advantage of row t_lo.  sink(i, tg, a)
+// sees every row: the loads of step t - 1.. do not depend on the carried advantage, so an unrolled body keeps several time
+// steps of loads in flight.  UNROLL is the loop's unroll count: 8 with lane = env (a wave walks all T rows), 1 in the scan, whose
+// lanes walk short chunks twice.
+template <int MODE, bool VNORM, int UNROLL, class Sink>
+__device__ __forceinline__ float td_gae_walk(TD_GAE_INPUTS, long e, long t_lo, long t_hi, float a, Sink sink)
+{
+    const float d_row = (MODE & PPO_GAE_DONE_PER_STEP) ? 0.0f : done[e];
+#pragma unroll UNROLL
+    for (long t = t_hi - 1; t >= t_lo; --t) {
+        const long i = t * N + e;
+        const float d = (MODE & PPO_GAE_DONE_PER_STEP) ? done[i] : d_row;
+        float tg;
+        a = td_gae_row<MODE, VNORM>(reward[i], v[i], v_next[i], d, tm, ts, gamma, gl, a, tg);
+        sink(i, tg, a);
+    }
+    return a;
+}
+
+// GAE as a wavefront scan, for the shapes where "lane = env" has nothing to run on: few envs, very long rollouts (the
+// reference's own 16-env configuration has T = 40 960, ppo.py:118-122).  One wave per env; the 64 lanes own 64 consecutive
+// chunks of the time axis, lane 0 the LAST one (time_scan.h).
+//   pass 1  every lane runs the recurrence over its chunk from a zero carry (its chunk's own contribution S_l) and forms the
+//           chunk's multiplier gl^len -- 64 chunks in parallel instead of one 40 960-long chain;
+//   carry   the carry into chunk l is A_l = S_{l+1} + c^{len(l+1)} A_{l+1}: affine_carry;
+//   pass 2  every lane reruns its chunk from the true carry, and sink(i, tg, a) sees every row exactly once.
+// Inside a chunk the arithmetic is the reference's (separately rounded mul/add); only the 63 carries are re-associated, so the
+// result agrees with the sequential loop to fp32 rounding (tested at 1e-5), not bit for bit: the host picks this form only when
+// N is small (PPO_GAE_SCAN).  The masked recurrence (PPO_GAE_MASK_RECURRENCE) has no scan form: MODE is 0 or 1.
+template <int MODE, bool VNORM, class Sink>
+__device__ __forceinline__ void td_gae_scan_env(TD_GAE_INPUTS, long e, const TimeChunk& c, int lane, Sink sink)
+{
+    static_assert((MODE & PPO_GAE_MASK_RECURRENCE) == 0, "the scan form does not mask the recurrence");
+    float m = 1.0f;
+    const float S = td_gae_walk<MODE, VNORM, 1>(reward, v, v_next, done, tm, ts, gamma, gl, N, e, c.t_lo, c.t_hi, 0.0f,
+                                                [&](long, float, float) { m *= gl; });
+    td_gae_walk<MODE, VNORM, 1>(reward, v, v_next, done, tm, ts, gamma, gl, N, e, c.t_lo, c.t_hi, affine_carry(m, S, lane), sink);
+}
+
+// The four kernels: a grid mapping around the walk or the scan each.  Plain: one env (block) per lane (workgroup), as many
+// workgroups as that takes.  Value-normalising (--normalize_value): always VALUE_NORM_SETS workgroups
+// that stride over the env blocks / envs -- one block for N <= 16384 -- and every lane keeps Welford moments of the targets it
+// wrote (not raw sums: targets of mean 1e3 / std 1e-2 keep their digits), one set per workgroup for value_norm_merge_kernel.
+constexpr int GAE_BLOCK = 64;               // one wave per workgroup: envs spread over the CUs
+
 template <int MODE>
 __global__ __launch_bounds__(256) void ppo_td_gae_kernel(
     const float* __restrict__ reward, const float* __restrict__ v, const float* __restrict__ v_next,
@@ -73,81 +145,60 @@ __global__ __launch_bounds__(256) void ppo_td_gae_kernel(
 {
     const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= N) return;
-    float d_row = (MODE & PPO_GAE_DONE_PER_STEP) ? 0.0f : done[e];
-    float a = 0.0f;
-#pragma unroll 8
-    for (long t = T - 1; t >= 0; --t) {
-        const long i = t * N + e;
-        float d = (MODE & PPO_GAE_DONE_PER_STEP) ? done[i] : d_row;
-        float tg = __fadd_rn(reward[i], __fmul_rn(__fmul_rn(gamma, v_next[i]), d));   // ppo.py:160
-        float delta = __fsub_rn(tg, v[i]);                                             // ppo.py:161
-        float carry = (MODE & PPO_GAE_MASK_RECURRENCE) ? __fmul_rn(a, d) : a;
-        a = __fadd_rn(__fmul_rn(gl, carry), delta);                                    // ppo.py:167
+    td_gae_walk<MODE, false, 8>(reward, v, v_next, done, 0.0f, 1.0f, gamma, gl, N, e, 0, T, 0.0f, [&](long i, float tg, float a) {
         target_out[i] = tg;
         adv_out[i] = a;
-    }
+    });
 }
 
-
-// GAE as a wavefront scan, for the shapes where "lane = env" has nothing to run on: few envs, very
-// long rollouts (the reference's own 16-env configuration has T = 40 960, ppo.py:118-122).  One wave
-// per env; the 64 lanes own 64 consecutive chunks of the time axis.
-//   pass 1  every lane runs the recurrence over its chunk from a zero carry (its chunk's own
-//           contribution S_l) -- 64 chunks in parallel instead of one 40 960-long chain;
-//   carry   the carry into chunk l is A_l = S_{l+1} + c^{len(l+1)} A_{l+1}, a linear recurrence over
-//           lanes, solved with a 6-step Kogge-Stone scan of (multiplier, value) pairs on shuffles;
-//   pass 2  every lane reruns its chunk from the true carry and writes target / advantage.
-// Inside a chunk the arithmetic is the reference's (separately rounded mul/add); only the 63 carries
-// are re-associated, so the result agrees with the sequential loop to fp32 rounding (tested at
-// 1e-5), not bit for bit: the host picks this kernel only when N is small (PPO_GAE_SCAN).
 template <int MODE>
-__global__ __launch_bounds__(64) void ppo_td_gae_scan_kernel(
+__global__ __launch_bounds__(GAE_BLOCK) void ppo_td_gae_scan_kernel(
     const float* __restrict__ reward, const float* __restrict__ v, const float* __restrict__ v_next,
     const float* __restrict__ done, float gamma, float gl, long T, long N,
     float* __restrict__ target_out, float* __restrict__ adv_out)
 {
-    const long e = blockIdx.x;
     const int lane = threadIdx.x;
-    const long L = (T + 63) / 64;
-    // reverse time: lane 0 owns the LAST chunk, so the scan runs towards higher lanes
-    const long t_hi = T - (long)lane * L;                 // exclusive
-    const long t_lo = (t_hi - L > 0) ? t_hi - L : 0;
-    const float d_row = (MODE & PPO_GAE_DONE_PER_STEP) ? 0.0f : done[e];
-    auto delta_at = [&](long t, float& tg) {
-        const long i = t * N + e;
-        const float d = (MODE & PPO_GAE_DONE_PER_STEP) ? done[i] : d_row;
-        tg = __fadd_rn(reward[i], __fmul_rn(__fmul_rn(gamma, v_next[i]), d));
-        return __fsub_rn(tg, v[i]);
-    };
-    // pass 1: chunk contribution and multiplier
-    float S = 0.0f, m = 1.0f;
-    for (long t = t_hi - 1; t >= t_lo && t_hi > 0; --t) {
-        float tg;
-        const float dl = delta_at(t, tg);
-        S = __fadd_rn(__fmul_rn(gl, S), dl);
-        m *= gl;
-    }
-    if (t_hi <= 0) { S = 0.0f; m = 1.0f; }
-    // inclusive scan over lanes (lane 0 first in reverse time): value after chunk l given zero
-    // carry into chunk 0:  X_l = S_l + m_l * X_{l-1}
-    float sm = m, sv = S;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float pm = __shfl_up(sm, o, 64), pv = __shfl_up(sv, o, 64);
-        if (lane >= o) { sv = sv + sm * pv; sm = sm * pm; }
-    }
-    float carry = __shfl_up(sv, 1, 64);                   // advantage entering this chunk
-    if (lane == 0) carry = 0.0f;
-    // pass 2: the real recurrence from the true carry
-    float a = carry;
-    for (long t = t_hi - 1; t >= t_lo && t_hi > 0; --t) {
-        float tg;
-        const float dl = delta_at(t, tg);
-        const float cin = (MODE & PPO_GAE_MASK_RECURRENCE) ? 0.0f : a;   // masked recurrence is not supported here
-        a = __fadd_rn(__fmul_rn(gl, cin), dl);
-        target_out[t * N + e] = tg;
-        adv_out[t * N + e] = a;
-    }
+    td_gae_scan_env<MODE, false>(reward, v, v_next, done, 0.0f, 1.0f, gamma, gl, N, blockIdx.x, reverse_chunk(T, lane), lane,
+                                 [&](long i, float tg, float a) {
+        target_out[i] = tg;
+        adv_out[i] = a;
+    });
+}
+
+template <int MODE>
+__global__ __launch_bounds__(GAE_BLOCK) void ppo_td_gae_vnorm_kernel(
+    const float* __restrict__ reward, const float* __restrict__ v, const float* __restrict__ v_next,
+    const float* __restrict__ done, const float* __restrict__ table, float gamma, float gl, long T, long N,
+    float* __restrict__ target_out, float* __restrict__ adv_out, double* __restrict__ sets)
+{
+    const float tm = table[0], ts = table[1];
+    double cn = 0.0, cm = 0.0, cq = 0.0;
+    for (long e = (long)blockIdx.x * GAE_BLOCK + threadIdx.x; e < N; e += (long)gridDim.x * GAE_BLOCK)
+        td_gae_walk<MODE, true, 8>(reward, v, v_next, done, tm, ts, gamma, gl, N, e, 0, T, 0.0f, [&](long i, float tg, float a) {
+            target_out[i] = tg;
+            adv_out[i] = a;
+            value_moments_add(cn, cm, cq, tg);
+        });
+    value_write_set(cn, cm, cq, sets + (long)blockIdx.x * VALUE_NORM_SET);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(GAE_BLOCK) void ppo_td_gae_vnorm_scan_kernel(
+    const float* __restrict__ reward, const float* __restrict__ v, const float* __restrict__ v_next,
+    const float* __restrict__ done, const float* __restrict__ table, float gamma, float gl, long T, long N,
+    float* __restrict__ target_out, float* __restrict__ adv_out, double* __restrict__ sets)
+{
+    const float tm = table[0], ts = table[1];
+    const int lane = threadIdx.x;
+    const TimeChunk c = reverse_chunk(T, lane);
+    double cn = 0.0, cm = 0.0, cq = 0.0;
+    for (long e = blockIdx.x; e < N; e += gridDim.x)
+        td_gae_scan_env<MODE, true>(reward, v, v_next, done, tm, ts, gamma, gl, N, e, c, lane, [&](long i, float tg, float a) {
+            target_out[i] = tg;
+            adv_out[i] = a;
+            value_moments_add(cn, cm, cq, tg);
+        });
+    value_write_set(cn, cm, cq, sets + (long)blockIdx.x * VALUE_NORM_SET);
 }
 
 // Advantage normalisation (named by BASELINE's north_star; the reference does NOT normalise,
@@ -170,18 +221,11 @@ __device__ __forceinline__ long adv_block_count(long n, int b)
 __global__ __launch_bounds__(256) void ppo_adv_stats_kernel(const float* __restrict__ adv, long n,
                                                             double* __restrict__ part)
 {
-    __shared__ double red[3][4];
     double cn = 0.0, cm = 0.0, cq = 0.0;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
         value_moments_add(cn, cm, cq, adv[i]);
-    for (int o = 32; o > 0; o >>= 1) {
-        const double nb = __shfl_down(cn, o, 64), mb = __shfl_down(cm, o, 64), qb = __shfl_down(cq, o, 64);
-        value_moments_merge(cn, cm, cq, nb, mb, qb);
-    }
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = cn; red[1][threadIdx.x >> 6] = cm; red[2][threadIdx.x >> 6] = cq; }
-    __syncthreads();
+    value_moments_to_thread0(cn, cm, cq);
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) value_moments_merge(cn, cm, cq, red[0][w], red[1][w], red[2][w]);
         part[2 * blockIdx.x] = cm;
         part[2 * blockIdx.x + 1] = cq;
     }
@@ -207,49 +251,13 @@ __global__ __launch_bounds__(64) void ppo_adv_totals_kernel(const double* __rest
     totals[1] = (float)(cq > 0.0 ? cq : 0.0);
 }
 
-// ppo.py:233 + :237 in one tiny launch: score += mean(reward)/num_eval_freq (kept on the device:
-// the reference's per-step .item() host sync is gone) and action_var = max(var_min, var - decay).
-// One workgroup, fixed reduction order: deterministic.
-__global__ __launch_bounds__(1024) void ppo_bookkeeping_kernel(const float* __restrict__ reward, long n,
-                                                               float* __restrict__ score_acc, float score_scale,
-                                                               float* __restrict__ action_var, int nvar,
-                                                               float var_decay, float var_min)
+// One row's score term, mean(row) * score_scale (ppo.py:233), by a workgroup of 1024 threads; thread 0 returns it, the others
+// 0.  16-byte loads where the row allows it, all of a thread's loads in flight at once (n = 8192 -> two float4 per thread), then
+// the wave tree and the 16 waves' sums in wave order: one fixed reduction order, so the term does not depend on who asks.
+__device__ __forceinline__ float score_row_term(const float* __restrict__ row, long n, float score_scale)
 {
     __shared__ float red[16];
     const int tid = threadIdx.x;
-    // 16-byte loads, all of a thread's loads in flight at once (n = 8192 -> two float4 per thread)
-    float s = 0.0f;
-    const long n4 = n >> 2;
-    const float4* r4 = reinterpret_cast<const float4*>(reward);
-    const bool aligned = (reinterpret_cast<uintptr_t>(reward) & 15) == 0;
-    if (aligned) {
-        for (long i = tid; i < n4; i += 1024) { const float4 v = r4[i]; s += (v.x + v.y) + (v.z + v.w); }
-        for (long i = 4 * n4 + tid; i < n; i += 1024) s += reward[i];
-    } else {
-        for (long i = tid; i < n; i += 1024) s += reward[i];
-    }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    if ((tid & 63) == 0) red[tid >> 6] = s;
-    __syncthreads();
-    if (tid == 0) {
-        float t = 0.0f;
-        for (int w = 0; w < 16; ++w) t += red[w];
-        *score_acc += t / (float)n * score_scale;
-    }
-    if (tid < nvar && var_decay > 0.0f) action_var[tid] = fmaxf(var_min, action_var[tid] - var_decay);
-}
-
-// The same bookkeeping for `rows` consecutive env steps at once (reward [rows][n]), bit for bit what
-// `rows` calls of the kernel above leave: one workgroup per row computes that row's score term with
-// the identical reduction, a second single-wave launch adds the terms in row order and applies the
-// variance decay `rows` times.  The rollout calls this when the score is printed and before an
-// update instead of paying a latency-bound single-workgroup launch on every env step.
-__global__ __launch_bounds__(1024) void ppo_row_terms_kernel(const float* __restrict__ reward, long n, float score_scale,
-                                                             float* __restrict__ terms)
-{
-    __shared__ float red[16];
-    const int tid = threadIdx.x;
-    const float* row = reward + (long)blockIdx.x * n;
     float s = 0.0f;
     const long n4 = n >> 2;
     const float4* r4 = reinterpret_cast<const float4*>(row);
@@ -263,11 +271,36 @@ __global__ __launch_bounds__(1024) void ppo_row_terms_kernel(const float* __rest
     for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
     if ((tid & 63) == 0) red[tid >> 6] = s;
     __syncthreads();
-    if (tid == 0) {
-        float t = 0.0f;
-        for (int w = 0; w < 16; ++w) t += red[w];
-        terms[blockIdx.x] = t / (float)n * score_scale;
-    }
+    if (tid != 0) return 0.0f;
+    float t = 0.0f;
+    for (int w = 0; w < 16; ++w) t += red[w];
+    return t / (float)n * score_scale;
+}
+
+// ppo.py:233 + :237 in one tiny launch: score += mean(reward)/num_eval_freq (kept on the device:
+// the reference's per-step .item() host sync is gone) and action_var = max(var_min, var - decay).
+// One workgroup, fixed reduction order: deterministic.
+__global__ __launch_bounds__(1024) void ppo_bookkeeping_kernel(const float* __restrict__ reward, long n,
+                                                               float* __restrict__ score_acc, float score_scale,
+                                                               float* __restrict__ action_var, int nvar,
+                                                               float var_decay, float var_min)
+{
+    const int tid = threadIdx.x;
+    const float term = score_row_term(reward, n, score_scale);
+    if (tid == 0) *score_acc += term;
+    if (tid < nvar && var_decay > 0.0f) action_var[tid] = fmaxf(var_min, action_var[tid] - var_decay);
+}
+
+// The same bookkeeping for `rows` consecutive env steps at once (reward [rows][n]), bit for bit what
+// `rows` calls of the kernel above leave: one workgroup per row computes that row's score term by
+// the same function, a second single-wave launch adds the terms in row order and applies the
+// variance decay `rows` times.  The rollout calls this when the score is printed and before an
+// update instead of paying a latency-bound single-workgroup launch on every env step.
+__global__ __launch_bounds__(1024) void ppo_row_terms_kernel(const float* __restrict__ reward, long n, float score_scale,
+                                                             float* __restrict__ terms)
+{
+    const float term = score_row_term(reward + (long)blockIdx.x * n, n, score_scale);
+    if (threadIdx.x == 0) terms[blockIdx.x] = term;
 }
 
 __global__ __launch_bounds__(64) void ppo_rows_apply_kernel(const float* __restrict__ terms, long rows,
@@ -294,29 +327,25 @@ extern "C" hipError_t flyhip_launch_rollout_bookkeeping(const float* reward, int
                                                         float* score_acc, float score_scale, float* action_var, int nvar,
                                                         float var_decay, float var_min, int* rows_applied, void* stream)
 {
-    hipLaunchKernelGGL(ppo_row_terms_kernel, dim3((unsigned)rows), dim3(1024), 0, (hipStream_t)stream, reward, (long)n,
-                       score_scale, terms);
-    hipLaunchKernelGGL(ppo_rows_apply_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, terms, (long)rows, score_acc,
-                       action_var, nvar, var_decay, var_min, rows_applied);
-    return hipGetLastError();
+    hipError_t e = launch_kernel<ppo_row_terms_kernel>((unsigned)rows, 1024, 0, stream, reward, (long)n, score_scale, terms);
+    if (e != hipSuccess) return e;
+    return launch_kernel<ppo_rows_apply_kernel>(1, 64, 0, stream, terms, (long)rows, score_acc, action_var, nvar, var_decay, var_min,
+                                                rows_applied);
 }
 
 extern "C" hipError_t flyhip_launch_bookkeeping(const float* reward, int64_t n, float* score_acc, float score_scale,
                                                 float* action_var, int nvar, float var_decay, float var_min,
                                                 void* stream)
 {
-    hipLaunchKernelGGL(ppo_bookkeeping_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, reward, (long)n, score_acc,
-                       score_scale, action_var, nvar, var_decay, var_min);
-    return hipGetLastError();
+    return launch_kernel<ppo_bookkeeping_kernel>(1, 1024, 0, stream, reward, (long)n, score_acc, score_scale, action_var, nvar,
+                                                 var_decay, var_min);
 }
 
 extern "C" hipError_t flyhip_launch_sample_logprob(const float* mu, const float* var, const float* eps,
                                                    float* act_out, float* logp_out, int64_t n, void* stream)
 {
     int grid = (int)((n + SL_BLOCK - 1) / SL_BLOCK);
-    hipLaunchKernelGGL(ppo_sample_logprob_kernel, dim3(grid), dim3(SL_BLOCK), 0, (hipStream_t)stream,
-                       mu, var, eps, act_out, logp_out, (long)n);
-    return hipGetLastError();
+    return launch_kernel<ppo_sample_logprob_kernel>(grid, SL_BLOCK, 0, stream, mu, var, eps, act_out, logp_out, (long)n);
 }
 
 extern "C" hipError_t flyhip_launch_td_gae(const float* reward, const float* v, const float* v_next,
@@ -326,29 +355,42 @@ extern "C" hipError_t flyhip_launch_td_gae(const float* reward, const float* v, 
     const float gl = (float)((double)gamma * (double)lambda);   // python double product, ppo.py:167
     if (mode & PPO_GAE_SCAN)
         return with_int<0, 1>(mode & PPO_GAE_DONE_PER_STEP ? 1 : 0, [&](auto m) {
-            return launch_kernel<ppo_td_gae_scan_kernel<m.value>>(dim3((unsigned)N), 64, 0, stream, reward, v, v_next, done, gamma, gl,
-                                                                  (long)T, (long)N, target_out, adv_out);
+            return launch_kernel<ppo_td_gae_scan_kernel<m.value>>(dim3((unsigned)N), GAE_BLOCK, 0, stream, reward, v, v_next, done, gamma,
+                                                                  gl, (long)T, (long)N, target_out, adv_out);
         });
-    int block = 64;                                              // one wave per workgroup: spread envs over CUs
-    int grid = (int)((N + block - 1) / block);
+    int grid = (int)((N + GAE_BLOCK - 1) / GAE_BLOCK);
     return with_int<0, 1, 2, 3>(mode & 3, [&](auto m) {
-        return launch_kernel<ppo_td_gae_kernel<m.value>>(grid, block, 0, stream, reward, v, v_next, done, gamma, gl, (long)T, (long)N,
+        return launch_kernel<ppo_td_gae_kernel<m.value>>(grid, GAE_BLOCK, 0, stream, reward, v, v_next, done, gamma, gl, (long)T, (long)N,
                                                          target_out, adv_out);
+    });
+}
+
+extern "C" hipError_t flyhip_launch_td_gae_vnorm(const float* reward, const float* v, const float* v_next, const float* done,
+                                                 const float* table, float gamma, float lambda, int64_t T, int64_t N,
+                                                 float* target_out, float* adv_out, double* sets, int mode, void* stream)
+{
+    const float gl = (float)((double)gamma * (double)lambda);   // python double product, ppo.py:167
+    // always FLY_VALUE_NORM_SETS workgroups: one set each, and those with no env write an empty set
+    if (mode & PPO_GAE_SCAN)
+        return with_int<0, 1>(mode & PPO_GAE_DONE_PER_STEP ? 1 : 0, [&](auto m) {
+            return launch_kernel<ppo_td_gae_vnorm_scan_kernel<m.value>>(VALUE_NORM_SETS, GAE_BLOCK, 0, stream, reward, v, v_next, done,
+                                                                        table, gamma, gl, (long)T, (long)N, target_out, adv_out, sets);
+        });
+    return with_int<0, 1, 2, 3>(mode & 3, [&](auto m) {
+        return launch_kernel<ppo_td_gae_vnorm_kernel<m.value>>(VALUE_NORM_SETS, GAE_BLOCK, 0, stream, reward, v, v_next, done, table,
+                                                               gamma, gl, (long)T, (long)N, target_out, adv_out, sets);
     });
 }
 
 extern "C" hipError_t flyhip_launch_adv_stats(const float* adv, int64_t n, float* stats, void* stream)
 {
     double* part = reinterpret_cast<double*>(stats + 2);         // the ABI checks that stats is 8-byte aligned
-    hipLaunchKernelGGL(ppo_adv_stats_kernel, dim3(ADV_BLOCKS), dim3(256), 0, (hipStream_t)stream, adv, (long)n, part);
-    hipError_t e = hipGetLastError();
+    hipError_t e = launch_kernel<ppo_adv_stats_kernel>(ADV_BLOCKS, 256, 0, stream, adv, (long)n, part);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(ppo_adv_totals_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, part, (long)n, stats);
-    return hipGetLastError();
+    return launch_kernel<ppo_adv_totals_kernel>(1, 64, 0, stream, part, (long)n, stats);
 }
 
 extern "C" hipError_t flyhip_launch_adv_apply(float* adv, int64_t n, const float* totals, float count, float eps, void* stream)
 {
-    hipLaunchKernelGGL(ppo_adv_apply_kernel, dim3(512), dim3(256), 0, (hipStream_t)stream, adv, (long)n, totals, count, eps);
-    return hipGetLastError();
+    return launch_kernel<ppo_adv_apply_kernel>(512, 256, 0, stream, adv, (long)n, totals, count, eps);
 }

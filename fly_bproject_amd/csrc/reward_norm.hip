@@ -14,12 +14,12 @@
 #include <stdint.h>
 #include "flyhip.h"
 #include "value_norm.h"
+#include "float4_map.h"
 #include "launch.h"
 
 namespace {
 
 constexpr int RETURNS_BLOCK = 64;           // one wave per workgroup, as episode_stats_kernel: envs spread over the CUs
-constexpr int SCALE_THREADS = 256;
 
 // one step of the return: the definition's two rounded ops
 __device__ __forceinline__ double return_step(double g, double G, float r)
@@ -122,23 +122,13 @@ __device__ __forceinline__ float reward_scale(float x, float r, float clip)
     return y < -clip ? -clip : y;
 }
 
-// out[i] = clamp(reward[i] * r, -clip, clip): 16-byte accesses where both buffers allow it, a scalar tail.  Every element is
-// read before it is written by the same thread, so out may be the reward buffer itself.
-__global__ __launch_bounds__(SCALE_THREADS) void reward_scale_kernel(const float* reward, long n,
-                                                                     const float* __restrict__ table, float clip, float* out)
+// out[i] = clamp(reward[i] * r, -clip, clip), elementwise (float4_map.h).  Every element is read before it is written by the
+// same thread, so out may be the reward buffer itself: the two pointers are not __restrict__.
+__global__ __launch_bounds__(FLOAT4_MAP_THREADS) void reward_scale_kernel(const float* reward, long n,
+                                                                          const float* __restrict__ table, float clip, float* out)
 {
     const float r = table[2];
-    const long stride = (long)gridDim.x * SCALE_THREADS, first = (long)blockIdx.x * SCALE_THREADS + threadIdx.x;
-    const bool aligned = ((reinterpret_cast<uintptr_t>(reward) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
-    const long n4 = aligned ? n >> 2 : 0;
-    const float4* in4 = reinterpret_cast<const float4*>(reward);
-    float4* out4 = reinterpret_cast<float4*>(out);
-    for (long i = first; i < n4; i += stride) {
-        const float4 x = in4[i];
-        out4[i] = make_float4(reward_scale(x.x, r, clip), reward_scale(x.y, r, clip), reward_scale(x.z, r, clip),
-                              reward_scale(x.w, r, clip));
-    }
-    for (long i = 4 * n4 + first; i < n; i += stride) out[i] = reward_scale(reward[i], r, clip);
+    float4_map(reward, n, out, [=](float x) { return reward_scale(x, r, clip); });
 }
 
 }  // namespace
@@ -159,8 +149,5 @@ extern "C" hipError_t flyhip_launch_reward_returns(const float* reward, const in
 extern "C" hipError_t flyhip_launch_reward_scale(const float* reward, int64_t n, const float* table, float clip, float* out,
                                                  void* stream)
 {
-    const long per = 4L * SCALE_THREADS;
-    long grid = (n + per - 1) / per;
-    if (grid > 1024) grid = 1024;
-    return launch_kernel<reward_scale_kernel>((unsigned)grid, SCALE_THREADS, 0, stream, reward, (long)n, table, clip, out);
+    return launch_kernel<reward_scale_kernel>(float4_map_grid(n), FLOAT4_MAP_THREADS, 0, stream, reward, (long)n, table, clip, out);
 }

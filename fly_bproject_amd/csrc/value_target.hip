@@ -2,7 +2,7 @@
 //
 //   lambda_targets_kernel      target = adv + vd elementwise, vd = v * s + m under the value-normalisation table (or v without
 //                              one), plus -- when asked for -- the float64 moments (count, mean, M2) of the targets, one set per
-//                              workgroup: the contract value_td_gae_kernel (value_norm.hip) gives ppo_value_norm_merge
+//                              workgroup: the contract ppo_td_gae_vnorm_kernel (ppo_kernels.hip) gives ppo_value_norm_merge
 //
 // A stand-alone pass behind the unchanged GAE kernels: it reads the advantages and critic outputs they read or wrote and
 // overwrites the TD targets (and their moment sets).  Deterministic: per-lane Welford updates, a fixed combination tree, no atomics.
@@ -14,8 +14,7 @@
 
 namespace {
 
-constexpr int TARGET_THREADS = 256;
-constexpr int TARGET_WAVES = TARGET_THREADS / 64;
+constexpr int TARGET_THREADS = 256;         // value_moments_to_thread0's workgroup
 
 // Separately rounded fp32 ops in this order, no fma: the denormalisation of ppo_td_gae_vnorm, then one add.  NaN passes through.
 template <bool TABLE>
@@ -24,20 +23,9 @@ __device__ __forceinline__ float lambda_target(float adv, float v, float m, floa
     return __fadd_rn(adv, TABLE ? value_denorm(v, m, s) : v);
 }
 
-// A wave's 64 per-lane moments -> its lane 0: the shuffle tree of value_write_set (value_norm.h), which writes a one-wave
-// workgroup's set itself; here four waves go on to be combined.
-__device__ __forceinline__ void moments_to_lane0(double& n, double& mean, double& m2)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double nb = __shfl_down(n, o, 64), mb = __shfl_down(mean, o, 64), qb = __shfl_down(m2, o, 64);
-        value_moments_merge(n, mean, m2, nb, mb, qb);
-    }
-}
-
-// Grid-stride over n elements: 16-byte accesses where all three buffers allow it (value_norm_apply_kernel's split), a scalar
-// tail; element by element the same ops either way.  Every lane keeps Welford moments of the targets it wrote; the four waves
-// reduce theirs by the shuffle tree, and thread 0 combines the four in wave order and writes the workgroup's set.
+// Grid-stride over n elements: 16-byte accesses where all three buffers allow it (float4_map.h's split, here with two inputs and
+// the moments), a scalar tail; element by element the same ops either way.  Every lane keeps Welford moments of the targets it
+// wrote; value_moments_to_thread0 (value_norm.h) reduces the four waves', and thread 0 writes the workgroup's set.
 template <bool TABLE, bool SETS>
 __global__ __launch_bounds__(TARGET_THREADS) void lambda_targets_kernel(const float* __restrict__ adv, const float* __restrict__ v,
                                                                          const float* __restrict__ table, long n,
@@ -70,17 +58,8 @@ __global__ __launch_bounds__(TARGET_THREADS) void lambda_targets_kernel(const fl
         if (SETS) value_moments_add(cn, cm, cq, t);
     }
     if (!SETS) return;
-    __shared__ double part[TARGET_WAVES][VALUE_NORM_SET];
-    moments_to_lane0(cn, cm, cq);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { part[wave][0] = cn; part[wave][1] = cm; part[wave][2] = cq; }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    for (int w = 1; w < TARGET_WAVES; ++w) value_moments_merge(cn, cm, cq, part[w][0], part[w][1], part[w][2]);
-    double* set = sets + (long)blockIdx.x * VALUE_NORM_SET;
-    set[0] = cn;
-    set[1] = cm;
-    set[2] = cq > 0.0 ? cq : 0.0;
+    value_moments_to_thread0(cn, cm, cq);
+    if (threadIdx.x == 0) value_store_set(cn, cm, cq, sets + (long)blockIdx.x * VALUE_NORM_SET);
 }
 
 }  // namespace

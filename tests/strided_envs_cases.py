@@ -2,9 +2,9 @@
 tests/test_strided_envs_cpu.py): PPO's post-rollout kernels that launch a fixed grid and stride over the envs beyond it.
 
     kernel                              one trip covers        workgroup g walks
-    value_td_gae_kernel<MODE>           a block of 64 envs     env blocks g, g + 256, ...
+    ppo_td_gae_vnorm_kernel<MODE>       a block of 64 envs     env blocks g, g + 256, ...
     gae_episodic_kernel<true>           a block of 64 envs     env blocks g, g + 256, ...
-    value_td_gae_scan_kernel<MODE>      one env                envs g, g + 256, ...
+    ppo_td_gae_vnorm_scan_kernel<MODE>  one env                envs g, g + 256, ...
     gae_episodic_scan_kernel<true>      one env                envs g, g + 256, ...
     episode_stats_scan_kernel           one env                envs g, g + 256, ...
     gae_episodic_scan_kernel<false>     one env                envs g, g + grid, ... with grid = min(N, 65536)

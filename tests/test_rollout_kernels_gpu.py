@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the rollout's PPO kernels (csrc/ppo_kernels.hip, and the GAE copies of csrc/value_norm.hip) through the C ABI
+"""GPU (-m gpu): the rollout's PPO kernels (csrc/ppo_kernels.hip, its value-normalising GAE instances included) through the C ABI
 against the float64 references of tests/rollout_ref.py, at ragged shapes and at the edges of their index arithmetic.
 
 Every buffer a kernel writes sits between two guards of 64 elements pre-filled with a sentinel, and reading a result back
@@ -251,8 +251,9 @@ def test_td_gae_scan_rejects_the_masked_recurrence(lib):
 
 @pytest.mark.parametrize("T", SCAN_T)
 def test_td_gae_vnorm_scan_copy_against_float64(lib, T):
-    """value_norm.hip carries its own copy of the scan kernel: under the identity table it is held to the same reference and
-    bound, equals ppo_td_gae's scan bit for bit, and counts every target exactly once in its moment sets."""
+    """The value-normalising instance of the scan (ppo_td_gae_vnorm_scan_kernel, once a copy in value_norm.hip, now the same
+    td_gae_scan_env in another grid mapping): under the identity table it is held to the same reference and bound, equals
+    ppo_td_gae's scan bit for bit, and counts every target exactly once in its moment sets."""
     N, mode = 3, T % 2
     r, v, vn, d, ref = gae_case(T, N, mode)
     tgt, adv, sets = run_gae_vnorm(lib, r, v, vn, d, mode | R.GAE_SCAN)

@@ -1,5 +1,5 @@
-"""GPU (-m gpu): PPO's fixed-grid post-rollout kernels past their first trip.  value_td_gae_kernel, value_td_gae_scan_kernel
-(csrc/value_norm.hip), gae_episodic_kernel<true>, gae_episodic_scan_kernel<true> / <false> (csrc/gae_episodic.hip) and
+"""GPU (-m gpu): PPO's fixed-grid post-rollout kernels past their first trip.  ppo_td_gae_vnorm_kernel, ppo_td_gae_vnorm_scan_kernel
+(csrc/ppo_kernels.hip), gae_episodic_kernel<true>, gae_episodic_scan_kernel<true> / <false> (csrc/gae_episodic.hip) and
 episode_stats_scan_kernel (csrc/episode_stats.hip) launch a fixed grid and stride over the envs beyond it, carrying float64
 moments or an episode set from one env (or block of 64 envs) to the next while everything else about an env starts afresh.
 The shapes of tests/strided_envs_cases.py are the smallest at which a workgroup makes a second and a third trip, with ragged
@@ -96,7 +96,7 @@ def _vn_gae(S_v, case, mode):
 @pytest.mark.parametrize("mode", [0, 1, 2, 3])
 @pytest.mark.parametrize("T,N,per", LANE)
 def test_td_gae_vnorm_lane(lib, T, N, per, mode):
-    what = "value_td_gae_kernel<%d> T=%d N=%d (%d trips)" % (mode, T, N, _trips(N, per))
+    what = "ppo_td_gae_vnorm_kernel<%d> T=%d N=%d (%d trips)" % (mode, T, N, _trips(N, per))
     case = S.td_case(T, N, mode)
     run = _vn_gae(S.TABLE_S, case, mode)
     tg, adv, sets = run
@@ -121,7 +121,7 @@ def test_td_gae_vnorm_lane(lib, T, N, per, mode):
 @pytest.mark.parametrize("mode", [0, 1])
 @pytest.mark.parametrize("T,N,per", SCAN)
 def test_td_gae_vnorm_scan(lib, T, N, per, mode):
-    what = "value_td_gae_scan_kernel<%d> T=%d N=%d (%d trips)" % (mode, T, N, _trips(N, per))
+    what = "ppo_td_gae_vnorm_scan_kernel<%d> T=%d N=%d (%d trips)" % (mode, T, N, _trips(N, per))
     case = S.td_case(T, N, mode)
     run = _vn_gae(S.TABLE_S, case, mode | R.GAE_SCAN)
     tg, adv, sets = run
