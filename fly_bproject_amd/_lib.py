@@ -1,5 +1,5 @@
-"""ctypes binding of libflyhip.so (include/flyhip.h, and include/flyhip_ext.h for what was added after its prototype list was
-fixed).  Fails loudly: no library, no product."""
+"""ctypes binding of libflyhip.so (include/flyhip.h, and include/flyhip_ext.h and include/flyhip_update_stats.h for what was added
+after its prototype list was fixed).  Fails loudly: no library, no product."""
 import ctypes as C
 import os
 
@@ -10,6 +10,7 @@ LIB_PATH = os.environ.get("FLYHIP_LIB") or os.path.join(_HERE, "libflyhip.so")
 _lib = None
 _api = None
 _ext = None
+_update_stats = None
 
 
 class FlyHipError(RuntimeError):
@@ -39,6 +40,8 @@ VALUE_NORM_TABLE = 4    # FLY_VALUE_NORM_TABLE: m | s | r | 0 (f32)
 VALUE_NORM_SETS = 256   # FLY_VALUE_NORM_SETS: moment sets one ppo_td_gae_vnorm writes
 EPISODE_SET = 10        # FLY_EPISODE_SET: n | ret_mean | ret_M2 | ret_min | ret_max | len_sum | len_min | len_max | timeouts | rows (f64)
 EPISODE_SETS = 256      # FLY_EPISODE_SETS: sets one ppo_episode_stats writes
+UPDATE_STATS_SET = 17   # FLY_UPDATE_STATS_SET: one set of update statistics (f64), include/flyhip_update_stats.h has the table
+UPDATE_STATS_SETS = 256 # FLY_UPDATE_STATS_SETS: sets one ppo_update_stats writes
 DR_PARAMS = 6           # FLY_DR_PARAMS: kp, kd, effort, mass (+ inertia), mu, gravity multipliers
 DR_ROW = 8              # FLY_DR_ROW: a randomisation table row, f32 m[6] | draw count (int32 bits) | 0
 ABI_VERSION = 13        # include/flyhip.h as this package binds it (fly_abi_version(): argument lists changed between versions)
@@ -117,6 +120,11 @@ SYMBOLS_EXT = {
     "ppo_reward_returns": [_P, _P, _F, _L, _L, _P, _P, _P, _I, _P],
     "ppo_reward_scale": [_P, _L, _P, _F, _P, _P],
 }
+# include/flyhip_update_stats.h: the update diagnostics (PPO --update_stats), bound the same way on update_stats_api()
+SYMBOLS_UPDATE_STATS = {
+    "ppo_update_stats": [_P, _P, _P, _P, _P, _P, _P, _F, _L, _P, _P],
+    "ppo_update_stats_merge": [_P, _L, _P, _P, _P, _P],
+}
 
 
 def build(verbose=False):
@@ -129,7 +137,7 @@ def build(verbose=False):
 
 
 def load():
-    global _lib, _api, _ext
+    global _lib, _api, _ext, _update_stats
     if _lib is not None:
         return _lib
     if not os.path.exists(LIB_PATH):
@@ -139,7 +147,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     lib.fly_last_error.restype = C.c_char_p
     lib.fly_last_error.argtypes = []
-    for name, argtypes in list(SYMBOLS.items()) + list(SYMBOLS_EXT.items()):
+    for name, argtypes in list(SYMBOLS.items()) + list(SYMBOLS_EXT.items()) + list(SYMBOLS_UPDATE_STATS.items()):
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.argtypes = argtypes
         fn.restype = C.c_int64 if name.endswith(("_workspace_floats", "_image_halves")) else C.c_int
@@ -152,12 +160,16 @@ def load():
     _ext = _Api()
     for name in SYMBOLS_EXT:
         setattr(_ext, name, _checked(name, getattr(lib, name), lib.fly_last_error))
+    _update_stats = _Api()
+    for name in SYMBOLS_UPDATE_STATS:
+        setattr(_update_stats, name, _checked(name, getattr(lib, name), lib.fly_last_error))
     _lib = lib
     return lib
 
 
 class _Api:
-    """One checked callable per SYMBOLS entry (api()), or per SYMBOLS_EXT entry (ext())."""
+    """One checked callable per SYMBOLS entry (api()), per SYMBOLS_EXT entry (ext()) or per SYMBOLS_UPDATE_STATS entry
+    (update_stats_api())."""
 
 
 def _checked(name, fn, last_error):
@@ -198,6 +210,13 @@ def ext():
     if _ext is None:
         load()
     return _ext
+
+
+def update_stats_api():
+    """api() for the entry points of include/flyhip_update_stats.h (SYMBOLS_UPDATE_STATS), on an object of their own."""
+    if _update_stats is None:
+        load()
+    return _update_stats
 
 
 def check(rc, what):

@@ -415,6 +415,42 @@ int ppo_reward_scale(const float* reward, int64_t n, const float* table, float c
     return FLY_OK;
 }
 
+int ppo_update_stats(const float* mu, const float* action, const float* old_logp, const float* adv, const float* v,
+                     const float* target, const float* var, float clip, int64_t R, double* sets, void* stream)
+{
+    if (!mu || !action || !old_logp || !adv || !v || !target || !var || !sets) return fail(FLY_E_ARG, "ppo_update_stats: null pointer");
+    if (R < 1) return fail(FLY_E_ARG, "ppo_update_stats: R must be > 0");
+    if (!(clip > 0.0f && clip < 1.0f)) return fail(FLY_E_ARG, "ppo_update_stats: clip must be in (0, 1) (got %g)", (double)clip);   // NaN too
+    if (R > (INT64_MAX >> 2) / 18) return fail(FLY_E_ARG, "ppo_update_stats: R * 18 floats overflow a byte offset");
+    if ((reinterpret_cast<uintptr_t>(mu) | reinterpret_cast<uintptr_t>(action) | reinterpret_cast<uintptr_t>(old_logp) |
+         reinterpret_cast<uintptr_t>(adv) | reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(target) |
+         reinterpret_cast<uintptr_t>(var)) & 3)
+        return fail(FLY_E_ARG, "ppo_update_stats: a float32 buffer is not 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(sets) & 7) return fail(FLY_E_ARG, "ppo_update_stats: sets is not 8-byte aligned");
+    hipError_t e = flyhip_launch_update_stats(mu, action, old_logp, adv, v, target, var, clip, R, sets, stream);
+    if (e != hipSuccess) return hip_fail(e, "ppo_update_stats launch");
+    return FLY_OK;
+}
+
+int ppo_update_stats_merge(const double* sets, int64_t nsets, double* last, double* window, double* total, void* stream)
+{
+    if (!sets || !last || !window || !total) return fail(FLY_E_ARG, "ppo_update_stats_merge: null pointer");
+    if (nsets < 1) return fail(FLY_E_ARG, "ppo_update_stats_merge: nsets must be > 0");
+    if (nsets > INT64_MAX / (FLY_UPDATE_STATS_SET * (int64_t)sizeof(double)))
+        return fail(FLY_E_ARG, "ppo_update_stats_merge: nsets * FLY_UPDATE_STATS_SET overflows int64");
+    if ((reinterpret_cast<uintptr_t>(sets) | reinterpret_cast<uintptr_t>(last) | reinterpret_cast<uintptr_t>(window) |
+         reinterpret_cast<uintptr_t>(total)) & 7)
+        return fail(FLY_E_ARG, "ppo_update_stats_merge: a float64 buffer is not 8-byte aligned");
+    const double* p[3] = {last, window, total};
+    for (int i = 0; i < 3; ++i)
+        for (int j = i + 1; j < 3; ++j)
+            if (p[i] < p[j] + FLY_UPDATE_STATS_SET && p[j] < p[i] + FLY_UPDATE_STATS_SET)
+                return fail(FLY_E_ARG, "ppo_update_stats_merge: last, window and total must not overlap");
+    hipError_t e = flyhip_launch_update_stats_merge(sets, nsets, last, window, total, stream);
+    if (e != hipSuccess) return hip_fail(e, "ppo_update_stats_merge launch");
+    return FLY_OK;
+}
+
 int ppo_minibatch_gather(const float* obs, const float* act, const float* logp, const float* adv, const float* target, int64_t R,
                          uint32_t seed, uint32_t epoch_key, int64_t first, int64_t n, float* obs_out, float* act_out,
                          float* logp_out, float* adv_out, float* target_out, int32_t* index_out, void* stream)

@@ -76,6 +76,13 @@ hipError_t flyhip_launch_reward_returns(const float* reward, const int64_t* rese
                                         const double* carry_in, double* carry_out, double* sets, int mode, void* stream);
 hipError_t flyhip_launch_reward_scale(const float* reward, int64_t n, const float* table, float clip, float* out, void* stream);
 
+// update_stats.hip
+hipError_t flyhip_launch_update_stats(const float* mu, const float* action, const float* old_logp, const float* adv,
+                                      const float* v, const float* target, const float* var, float clip, int64_t R, double* sets,
+                                      void* stream);
+hipError_t flyhip_launch_update_stats_merge(const double* sets, int64_t nsets, double* last, double* window, double* total,
+                                            void* stream);
+
 // minibatch_gather.hip
 hipError_t flyhip_launch_minibatch_gather(const float* obs, const float* act, const float* logp, const float* adv,
                                           const float* target, int64_t R, uint32_t seed, uint32_t epoch_key, int64_t first,

@@ -39,7 +39,7 @@ OPTIONS = (
     Option("action_noise", "white", ("white", "ar1")), Option("noise_rho", 0.5),
     Option("normalize_obs", False), Option("obs_clip", 5.0), Option("normalize_value", False),
     Option("normalize_advantage", False), Option("lambda_returns", False), Option("episode_stats", False),
-    Option("normalize_reward", False), Option("reward_clip", 10.0),
+    Option("normalize_reward", False), Option("reward_clip", 10.0), Option("update_stats", False),
     Option("graph", False), Option("reuse_rollout_values", True), Option("log_throughput", False),
     Option("persistent_rollout", True, env="FLY_PERSISTENT_ROLLOUT"), Option("async_log", True, env="FLY_ASYNC_LOG"),
     Option("update_backend", "hip"), Option("dp_mode", "grad_allreduce", ("grad_allreduce", "param_average")),
@@ -151,6 +151,7 @@ class Options(EnvOptions):
     episode_stats: bool             # observes only: not part of a training state's meta (projection)
     normalize_reward: bool          # not in the meta either: a training state says it by holding agent["reward_norm"]
     reward_clip: float              # a launch argument, not state: a resume may change it
+    update_stats: bool              # observes only, like episode_stats: not in the meta
     graph: bool
     reuse_rollout_values: bool
     log_throughput: bool
@@ -223,7 +224,7 @@ def resolve(args, environ):
         action_noise=action_noise, noise_rho=noise_rho, normalize_obs=normalize_obs, obs_clip=obs_clip,
         normalize_value=bool(_get(args, "normalize_value")), normalize_advantage=bool(_get(args, "normalize_advantage")),
         lambda_returns=bool(_get(args, "lambda_returns")), episode_stats=bool(_get(args, "episode_stats")),
-        normalize_reward=normalize_reward, reward_clip=reward_clip,
+        normalize_reward=normalize_reward, reward_clip=reward_clip, update_stats=bool(_get(args, "update_stats")),
         graph=graph, reuse_rollout_values=bool(_get(args, "reuse_rollout_values")), log_throughput=bool(_get(args, "log_throughput")),
         async_log=bool(_wanted(args, environ, "async_log")), update_backend=_get(args, "update_backend"), dp_mode=dp_mode,
         dp_allreduce=dp_allreduce, gemm=gemm, step_gemm=step_gemm, mini_chunk_size=mini_chunk_size, rollout_size=rollout_size,

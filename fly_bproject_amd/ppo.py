@@ -127,6 +127,40 @@ def normalize_obs_ref(x, table):
     return ((x - table[:k]) * table[k:2 * k]).clamp(-clip, clip)
 
 
+def update_stats_entries(s):
+    """One set of update statistics (FLY_UPDATE_STATS_SET numbers, include/flyhip_update_stats.h) as agent.update_stats()
+    reports it: Python numbers; means are over the finite rows, and without one everything but the two counts is nan."""
+    rows, bad = int(s[0]), int(s[14])
+    n = rows - bad
+    nan = float("nan")
+    if n <= 0:
+        out = dict.fromkeys(("approx_kl", "kl_k1", "clip_fraction", "ratio_min", "ratio_max", "policy_loss", "value_loss", "loss",
+                             "explained_variance", "target_mean", "target_std", "adv_absmax", "target_absmax"), nan)
+        return dict(out, rows=rows, nonfinite=bad)
+    pol, hub, m2 = float(s[6]) / n, float(s[7]) / n, float(s[10])
+    return {"rows": rows, "nonfinite": bad, "approx_kl": float(s[2]) / n, "kl_k1": float(s[1]) / n,
+            "clip_fraction": float(s[3]) / n, "ratio_min": float(s[4]), "ratio_max": float(s[5]), "policy_loss": pol,
+            "value_loss": hub, "loss": pol + hub, "explained_variance": 1.0 - float(s[13]) / m2 if m2 > 0.0 else nan,
+            "target_mean": float(s[9]), "target_std": (max(m2, 0.0) / n) ** 0.5, "adv_absmax": float(s[15]),
+            "target_absmax": float(s[16])}
+
+
+def update_stats_suffix(w):
+    """' | KL ... | Clip ...% | EV ... | Loss ...' of the score line from a set's numbers; ' | KL n/a' for a set without rows."""
+    if int(w[0]) == 0:
+        return " | KL n/a"
+    e = update_stats_entries(w)
+    text = " | KL {:.5f} | Clip {:.1f}% | EV {:.3f} | Loss {:.4f}".format(e["approx_kl"], 100.0 * e["clip_fraction"],
+                                                                        e["explained_variance"], e["loss"])
+    return text + (" | Nonfinite {}".format(e["nonfinite"]) if e["nonfinite"] > 0 else "")
+
+
+def update_stats_empty():
+    """The empty set of update statistics."""
+    inf = float("inf")
+    return torch.tensor([0.0, 0.0, 0.0, 0.0, inf, -inf] + [0.0] * 11, dtype=torch.float64)
+
+
 def combine_adv_stats(ranks, count):
     """The all-rank (sum, M2) of the advantages from every rank's ppo_adv_stats pair: `ranks` [world][2] holds
     (sum_r, M2_r) over `count` elements each, M2 the centred second moment.  M2 = sum_r M2_r + count (mean_r - mean)^2
@@ -229,6 +263,12 @@ class PPO:
         self._episode_stats = opts.episode_stats
         if self._episode_stats:
             self._setup_episode_stats()
+        # opt-in (`update_stats`): how far the finished update moved the policy, how much of the surrogate was clipped and how
+        # well the critic fits its targets, from one forward of the updated network over the rollout's rows and one reduction
+        # behind every update, on the score line and through update_stats().  It observes, as episode_stats.
+        self._update_stats = opts.update_stats
+        if self._update_stats:
+            self._setup_update_stats()
         # opt-in (`normalize_reward`, gymnasium's NormalizeReward / SB3's norm_reward): the GAE pass reads the rewards divided by
         # the running standard deviation of the discounted return, clamped to +-reward_clip.  all_reward keeps
         # the raw rows: score line, episode statistics and recorder read what they always did.  See _setup_reward_norm.
@@ -663,6 +703,42 @@ class PPO:
         return {"window": entries(self._ep_window.tolist()), "total": entries(self._ep_total.tolist())}
 
     # ------------------------------------------------------------------------------------------
+    # update diagnostics (opt-in)
+    def _setup_update_stats(self):
+        """The sets one ppo_update_stats launch writes and the three persistent sets, all the empty set: `last` (the latest
+        update), `window` (the updates since the last score line) and `total` (since the start of the run)."""
+        dev = self.device
+        self._us_sets = torch.zeros((_lib.UPDATE_STATS_SETS, _lib.UPDATE_STATS_SET), dtype=torch.float64, device=dev)
+        self._us_empty = update_stats_empty().to(dev)
+        self._us_last, self._us_window, self._us_total = (self._us_empty.clone() for _ in range(3))
+        self._us_mu = self._us_v = None                             # the probe's forward of the latest update
+
+    def _update_stats_probe(self, obs, action, old_log_prob, target, advantage):
+        """Behind the finished update: the UPDATED network over ALL T * N rows the update was handed (the normalised rows under
+        normalize_obs; the 16th chunk too, which the reference's minibatches never train on, Q3), through the unchanged
+        mlp_forward, one ppo_update_stats over them against the targets the update regressed on, and all ranks' sets in rank
+        order into `last`, `window` and `total`: every rank holds the same three sets.  On the stream, no host sync; nothing a
+        rollout or an update reads is written."""
+        api = _lib.update_stats_api()
+        with torch.no_grad():
+            self._us_mu, self._us_v = self.policy.forward(obs, want_mu=True, want_v=True)
+            rows = self._us_v.numel()
+            api.ppo_update_stats(self._us_mu, action, old_log_prob, advantage, self._us_v, target, self._action_var, self.clip, rows,
+                                 self._us_sets, _lib.stream_ptr())
+            sets = self._all_rank_sets(self._us_sets, "_keep_us_sets")
+            api.ppo_update_stats_merge(sets, sets.shape[0], self._us_last, self._us_window, self._us_total, _lib.stream_ptr())
+
+    def update_stats(self):
+        """{"last": {...}, "window": {...}, "total": {...}}: the latest update, the updates since the last score line and since
+        the start of the run, as Python numbers (update_stats_entries: rows, nonfinite, approx_kl -- Schulman's k3 --, kl_k1,
+        clip_fraction, ratio_min, ratio_max, policy_loss, value_loss, loss, explained_variance -- of the UPDATED critic on the
+        targets it just regressed on, in their units --, target_mean, target_std, adv_absmax, target_absmax).
+        Host-synchronising.  None when `update_stats` is off."""
+        if not self._update_stats:
+            return None
+        return {k: update_stats_entries(getattr(self, "_us_" + k).tolist()) for k in ("last", "window", "total")}
+
+    # ------------------------------------------------------------------------------------------
     @property
     def action_var(self):
         self._flush_bookkeeping()
@@ -780,6 +856,8 @@ class PPO:
             self._update_hip(obs, action, old_log_prob, target, advantage)
         else:
             self._update_torch(obs, action, old_log_prob, target, advantage)
+        if self._update_stats:
+            self._update_stats_probe(obs, action, old_log_prob, target, advantage)
         if self.minibatch == "shuffled":
             self._mb_update += 1                                    # the next update's epoch keys
         if self.normalize_obs:
@@ -1160,6 +1238,9 @@ class PPO:
             if self._episode_stats:
                 suffix += self._episode_suffix(self._ep_window.tolist())
                 self._ep_window.copy_(self._ep_empty)
+            if self._update_stats:
+                suffix += update_stats_suffix(self._us_window.tolist())
+                self._us_window.copy_(self._us_empty)
             if rank0:
                 print(self.SCORE_LINE.format(self.run_step, self.optim_step, score, self._action_var[0].item()) + suffix)
             return
@@ -1172,10 +1253,15 @@ class PPO:
             window = torch.empty(_lib.EPISODE_SET, dtype=torch.float64, pin_memory=True)
             window.copy_(self._ep_window, non_blocking=True)
             self._ep_window.copy_(self._ep_empty)
+        us_window = None
+        if self._update_stats:
+            us_window = torch.empty(_lib.UPDATE_STATS_SET, dtype=torch.float64, pin_memory=True)
+            us_window.copy_(self._us_window, non_blocking=True)
+            self._us_window.copy_(self._us_empty)
         ev = torch.cuda.Event()
         ev.record()
         self._score_acc.zero_()
-        self._log_q.append((ev, host, dev_vals, self.run_step, self.optim_step, rank0, suffix, window))
+        self._log_q.append((ev, host, dev_vals, self.run_step, self.optim_step, rank0, suffix, window, us_window))
         self._drain_log()
 
     def _drain_log(self, block=False):
@@ -1186,13 +1272,15 @@ class PPO:
             if isinstance(head, str):
                 print(head)
             else:
-                ev, host, _keep, run_step, optim_step, rank0, suffix, window = head
+                ev, host, _keep, run_step, optim_step, rank0, suffix, window, us_window = head
                 if block:
                     ev.synchronize()
                 elif not ev.query():
                     return
                 if window is not None:
                     suffix += self._episode_suffix(window.tolist())
+                if us_window is not None:
+                    suffix += update_stats_suffix(us_window.tolist())
                 if rank0:
                     print(self.SCORE_LINE.format(run_step, optim_step, float(host[0]), float(host[1])) + suffix)
             q.popleft()
@@ -1385,6 +1473,8 @@ class PPO:
             agent["reward_norm"] = {k: pack(getattr(self, "_rnorm_" + k)) for k in train_state.REWARD_NORM_KEYS}
         if self._episode_stats:
             agent["episode_stats"] = {k: pack(getattr(self, "_ep_" + k)) for k in ("carry_ret", "carry_len", "window", "total")}
+        if self._update_stats:
+            agent["update_stats"] = {k: pack(getattr(self, "_us_" + k)) for k in ("last", "window", "total")}
         state = {"format": train_state.FORMAT, "meta": self._training_state_meta(),
                  "meta_ext": train_state.expected_meta_ext(self.args), "policy": self.policy.training_state(),
                  "agent": agent, "env": self.env.training_state()}
@@ -1466,6 +1556,15 @@ class PPO:
                     self._ep_total.copy_(self._ep_empty)
                 print("episode_stats: the training state holds no episode statistics; each env's first closed return after "
                       "the resume is partial (its length is whole)")
+        if self._update_stats:
+            if isinstance(agent.get("update_stats"), dict):
+                for k in ("last", "window", "total"):
+                    restore(getattr(self, "_us_" + k), agent["update_stats"], "agent.update_stats", k)
+            else:
+                with torch.no_grad():
+                    for k in ("last", "window", "total"):
+                        getattr(self, "_us_" + k).copy_(self._us_empty)
+                print("update_stats: the training state holds no update statistics; the totals start at this resume")
         self._rate_mark = None
         torch.cuda.synchronize(self.device)
 

@@ -813,5 +813,7 @@ int dp_allreduce_p2p(float* grad, int64_t n_floats, void* const* windows, int32_
 
 /* entry points added since this file's prototype list was fixed (running reward scaling): declared in a file of their own */
 #include "flyhip_ext.h"
+/* PPO update diagnostics (--update_stats): likewise */
+#include "flyhip_update_stats.h"
 
 #endif /* FLYHIP_H */

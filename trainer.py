@@ -28,6 +28,12 @@ saved with or without the flag resumes with or without it.
 3.3i; off by default) with `--reward_clip` (the bound of a scaled reward, default 10.0).  Score line, `--episode_stats` and the
 recorder keep the raw rewards.  The statistics are saved with the checkpoint as reward_rms.* and loaded with it; such a
 checkpoint needs `--normalize_reward` to load, and a `--save_state` state resumes only under the flag it was saved with.
+`--update_stats` (PPO update diagnostics; off by default): behind every finished update one forward of the
+updated network over all rows of the rollout and one reduction; the score line also carries
+` | KL k3 | Clip pct% | EV ev | Loss loss` over the updates since the previous score line (` | KL n/a` without one, as under
+`--testing`; ` | Nonfinite n` when rows were non-finite).  The explained variance is that of the UPDATED critic on the targets
+it just regressed on (SB3 prints the pre-update critic's: this number one update later).  It observes and steers nothing;
+`--save_state` carries the sets, and a state saved with or without the flag resumes with or without it.
 `--gae episodic` (episode-aware advantage estimate with time-limit bootstrapping; the default `reference` is
 the reference's estimator with its quirks).
 `--minibatch shuffled` (every epoch draws its 15 minibatches from a fresh permutation of ALL rows of the rollout, DESIGN.md
@@ -132,6 +138,11 @@ def parse_args(argv=None):
               'episodes that finished since the previous score line (every step of an episode counts, the one that '
               'performs the reset too: rl_games current_rewards); one kernel over the reward and flag rows at the end of a '
               'rollout, no host sync; changes nothing the rollout or the update reads (DESIGN.md 3.3h); off by default')
+    flag('update_stats', action='store_true',
+         help='the score line also carries the approximate KL (Schulman k3), the clip fraction, the explained variance of the '
+              'updated critic on its targets and the loss over all rows of the rollout, from one forward of the updated network '
+              'and one reduction behind every update; no host sync; changes nothing the rollout or the update reads '
+              '(DESIGN.md 3.3j); off by default')
     flag('normalize_reward', action='store_true',
          help='the GAE pass reads rewards divided by the running standard deviation of the discounted return, clamped to '
               '+-reward_clip (gymnasium NormalizeReward, SB3 VecNormalize(norm_reward=True); no mean-centring).  The score '
