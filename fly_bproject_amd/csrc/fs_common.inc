@@ -516,7 +516,7 @@ __device__ __forceinline__ void fs_dw_v_fill(f32x16& acc, const bf16x8 (&z)[3], 
 }
 
 // all-reduce over 8 consecutive lanes (half a DPP row), every lane gets the same bits; the pairing (lane ^ 1, ^ 2, then the
-// two quads) is the xor-butterfly's, so sums come out bit for bit as the 32-lane butterfly of backward_body_b3 leaves them
+// two quads) is the xor-butterfly's, so sums come out bit for bit as the 32-lane butterfly of backward_body<ArithB3> leaves them
 __device__ __forceinline__ float fs_sum8(float x)
 {
     x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]

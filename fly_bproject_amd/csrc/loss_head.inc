@@ -5,7 +5,7 @@
 //
 //   huber / huber_grad     every update kernel (PPO value term, DQN TD term), through the two row functions below
 //   gauss_logp             ppo_row_loss and the rollout's sampling epilogues (mlp_forward.inc, mlp_fused_step.inc)
-//   ppo_row_loss           the loss phase of backward_body / backward_body_b3 (ppo_loss_phase, mlp_backward.inc: mlp_backward_dx*
+//   ppo_row_loss           the loss phase of backward_body, both arithmetics (ppo_loss_phase, mlp_backward.inc: mlp_backward_dx*
 //   ppo_mean_dz4           and mlp_fwd_bwd_kernel) and phase P5 of mlp_fused_step_kernel and mlp_fused_step_h2_kernel
 //   dqn_action_index       dqn_huber_td_kernel (dqn_kernels.hip), dqn_td_kernel (dqn_mfma.hip), dqn_chain_kernel (dqn_fused.inc)
 //   dqn_td_row             and dqn_chain_h2_kernel (dqn_fused_h2.inc)

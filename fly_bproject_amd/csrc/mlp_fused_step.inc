@@ -20,7 +20,7 @@
 // HBM traffic per optimizer step: x 12 MB + 4 MB of per-row scalars in, 76 MB of slabs out and 76 MB back in.
 // No cross-workgroup communication, so none of the flag / liveness machinery of mlp_fwd_bwd_kernel.
 //
-// Chain values (h1..h3, out, dz4..dz1) are bit-identical to forward_body_b3 / backward_body_b3 (same operands, same
+// Chain values (h1..h3, out, dz4..dz1) are bit-identical to forward_body<ArithB3> / backward_body<ArithB3> (same operands, same
 // MFMA order, same epilogue arithmetic): the DUMP instantiation writes them to HBM in tile-fragment order for the test
 // that holds the two paths together.  dW differs from mlp_grad_w_b3 only in summation order (per-CU tile sets
 // instead of row slabs).
@@ -73,7 +73,7 @@ __device__ __forceinline__ void fs_epilogue_elu(const f32x16& hi, const f32x16& 
 }
 
 // The dZ epilogue (lane = row): dZ = (hi + lo) * ELU'(H), H recombined from its three term planes, dZ split into its own -- the
-// arithmetic and order of backward_body_b3's epilogue -- as 4 column groups x 11 slices
+// arithmetic and order of backward_body<ArithB3>'s epilogue -- as 4 column groups x 11 slices
 template <int PITCH, bool DUMP>
 struct FsDactSlices {
     static constexpr int NS = 11;
@@ -756,11 +756,11 @@ __global__ __launch_bounds__(THREADS, 1) void mlp_fused_step_kernel(
 // ---------------------------------------------------------------------------------------------------------------
 // The rollout's policy for ONE 32-env tile in the style of the fused step (ppo.py:213-220: Net.pi + Net.v on the tile's
 // observation rows, sampling, log-prob, clipping): the X / H1 / H2 / H3 images as swizzled three-term planes in LDS, the chain GEMMs
-// of the fused step (fs_gemm, the same MFMA order and epilogues: every value equals forward_body_b3's, bit for bit), layer 4 as
-// split-K partials, then forward_body_b3's last phase (outputs, sampling on the 32 lanes of a row).  For the one-launch rollout at
+// of the fused step (fs_gemm, the same MFMA order and epilogues: every value equals forward_body<ArithB3>'s, bit for bit), layer 4 as
+// split-K partials, then forward_body<ArithB3>'s last phase (outputs, sampling on the 32 lanes of a row).  For the one-launch rollout at
 // one workgroup per CU (rollout_all_kernel): the tile's rows come from the fp32 block the env step of the same workgroup left in
 // LDS (`obs`, in H2's region: the conversion precedes the first store into H2), or from HBM row `x` for the first step; the
-// clipped actions also go to `acts` in LDS for the env step that follows.  ~20 % fewer cycles than forward_body_b3 (its 136-column
+// clipped actions also go to `acts` in LDS for the env step that follows.  ~20 % fewer cycles than forward_body<ArithB3> (its 136-column
 // pitches, builtin MFMAs behind a compiler-scheduled ring and two-half layer 1 / 2 interleave were tuned for three workgroups per CU).
 constexpr int FR_OFF_X = 0;
 constexpr int FR_OFF_H1 = FR_OFF_X + FS_X_HALVES;
@@ -837,7 +837,7 @@ __device__ __forceinline__ void policy_tile_fs(const FrLds& L, const long tile, 
         float lg = tid < MLP_NACT ? logf(s) : 0.0f;
         L.lg[tid] = lg;
         // sum_j log sqrt(var_j): the same for every row; summed ONCE, in the order of the 32-lane xor butterfly that
-        // forward_body_b3 runs per row (bit-identical log-probs)
+        // forward_body<ArithB3> runs per row (bit-identical log-probs)
 #pragma unroll
         for (int o = 1; o < 32; o <<= 1) lg += __shfl_xor(lg, o, 32);
         if (tid == 0) L.hld[0] = lg;
@@ -890,7 +890,7 @@ __device__ __forceinline__ void policy_tile_fs(const FrLds& L, const long tile, 
     }
     __syncthreads();
     stamp<STAMP>(stamps, 5);
-    // outputs + sampling (ppo.py:213-220): forward_body_b3's last phase re-laid on eight lanes per row, four output columns each --
+    // outputs + sampling (ppo.py:213-220): forward_body<ArithB3>'s last phase re-laid on eight lanes per row, four output columns each --
     // ONE pass, 16-byte LDS reads, and the row's Mahalanobis sum as an 8-lane DPP butterfly (no LDS round trips) in the pairing
     // order of the 32-lane xor butterfly (columns pair as (0,1),(2,3) in the lane, then lanes ^1, ^2, ^4): bit-identical sums
     {

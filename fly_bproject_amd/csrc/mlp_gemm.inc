@@ -162,10 +162,6 @@ __device__ __forceinline__ int frag_off(int row, int col) { return ((col >> 3) *
 // generic C/D map (A operand indexes rows): row (reg&3) + 8*(reg>>2) + 4*(lane>>5), column lane&31
 __device__ __forceinline__ int acc_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
 
-// bias + ELU epilogue: writes the activation tile to LDS (the next layer's operand), 16 bytes per
-// store, and -- when `gdst` is given -- the same 16 bytes to the saved-activation rows in HBM.  A
-// wave's four stores of one column tile touch the same 32 lines (one 128-byte line per row) and
-// together fill them, so L2 merges them into full-line writes; no LDS read-back pass is needed.
 // ---------------------------------------------------------------------------------------------
 // bf16x3 GEMM path: the same tile GEMMs on v_mfma_f32_32x32x16_bf16 with both operands split into
 // three bf16 terms (mlp_layout.h).  Six MFMAs of 8 passes per 16-wide k block replace eight fp32
@@ -311,6 +307,10 @@ __device__ __forceinline__ void epilogue_elu_b3(const f32x16& hi, const f32x16& 
     }
 }
 
+// bias + ELU epilogue: writes the activation tile to LDS (the next layer's operand), 16 bytes per
+// store, and -- when `gdst` is given -- the same 16 bytes to the saved-activation rows in HBM.  A
+// wave's four stores of one column tile touch the same 32 lines (one 128-byte line per row) and
+// together fill them, so L2 merges them into full-line writes; no LDS read-back pass is needed.
 // `gtile` points at this tile's first row of the destination (a wave-uniform pointer); lanes
 // address it with small 32-bit offsets, and all stores sit under ONE predicate (`nvalid` rows of
 // the tile exist): 64-bit per-lane address arithmetic and per-store exec masking are issue slots
@@ -340,5 +340,78 @@ __device__ __forceinline__ void epilogue_elu(const f32x16 (&acc)[NT], const floa
         for (int t = 0; t < NT; ++t)
 #pragma unroll
             for (int g = 0; g < 4; ++g) gstore4<COH>(gtile, go + t * 1024 + g * 256, y[t][g]);
+    }
+}
+
+// dZ = dA * ELU'(H).  H is read from the saved activations in exactly the accumulator layout (a
+// lane owns row lane&31 and four consecutive columns per register group): one 16-byte load per
+// group, requested before the GEMM whose epilogue consumes it.  The four loads of a column tile
+// touch one 128-byte line per row, so L1 serves three of them.
+template <int NT>
+struct HFrag { float4 v[NT][4]; };
+
+template <int N, int NT, bool COH = false>
+__device__ __forceinline__ void hfrag_load(HFrag<NT>& hf, const float* __restrict__ htile, int nvalid, int col0, int lane)
+{
+    // the saved activations are in tile-fragment order (frag_off, above): this wave's four loads of a
+    // column tile are four contiguous KiB.  Rows past the end of the batch read whatever the
+    // (allocated) rest of the last tile holds: their results are never stored and a row of an
+    // MFMA only feeds the same row.
+    const int go = (col0 / 32) * 1024 + lane * 4;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) hf.v[t][g] = gload4<COH>(htile, go + t * 1024 + g * 256);
+}
+
+// writes dZ to the gradient rows in HBM and (lds_out != nullptr) to the LDS tile the next GEMM reads
+template <int N, int NT>
+__device__ __forceinline__ void epilogue_dact(const f32x16 (&acc)[NT], const HFrag<NT>& hf, int col0, float* lds_out,
+                                              float* __restrict__ gtile, int nvalid, int lane)
+{
+    const int r = lane & 31;
+    float4 z[NT][4];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int nb = col0 + 32 * t + acc_n(g, lane);
+            const float4 hv = hf.v[t][g];
+            z[t][g].x = dact(acc[t][4 * g + 0], hv.x);
+            z[t][g].y = dact(acc[t][4 * g + 1], hv.y);
+            z[t][g].z = dact(acc[t][4 * g + 2], hv.z);
+            z[t][g].w = dact(acc[t][4 * g + 3], hv.w);
+            if (lds_out) *reinterpret_cast<float4*>(lds_out + r * (N + 4) + nb) = z[t][g];
+        }
+    }
+    if (r < nvalid) {
+        float* gl = gtile + (col0 / 32) * 1024 + lane * 4;
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) GSTORE4(gl + t * 1024 + g * 256, z[t][g]);
+    }
+}
+
+// dZ = (hi + lo) * ELU'(H) of the bf16x3 path: fp32 rows to HBM, three bf16 terms to the next GEMM's LDS tile
+template <int N>
+__device__ __forceinline__ void epilogue_dact_b3(const f32x16& hi, const f32x16& lo, const HFrag<1>& hf, int col0,
+                                                 u16* lds_plane0, float* __restrict__ gtile, int nvalid, int lane)
+{
+    const int r = lane & 31;
+    float4 z[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const float4 hv = hf.v[0][g];
+        z[g].x = dact(hi[4 * g + 0] + lo[4 * g + 0], hv.x);
+        z[g].y = dact(hi[4 * g + 1] + lo[4 * g + 1], hv.y);
+        z[g].z = dact(hi[4 * g + 2] + lo[4 * g + 2], hv.z);
+        z[g].w = dact(hi[4 * g + 3] + lo[4 * g + 3], hv.w);
+        if (lds_plane0) store_split4<N>(lds_plane0, r, col0 + acc_n(g, lane), z[g]);
+    }
+    if (r < nvalid) {
+        float* gl = gtile + (col0 / 32) * 1024 + lane * 4;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) GSTORE4(gl + g * 256, z[g]);
     }
 }

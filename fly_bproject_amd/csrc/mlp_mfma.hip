@@ -9,8 +9,8 @@
 //   mlp_forward.inc   all four layers of a 32-row tile in one workgroup: activations stay in LDS
 //                     between layers, weights stream from L2 in fragment order (mlp_layout.h),
 //                     layers 1/2 in two halves of 128 hidden columns, layer 4 split-K over the waves,
-//                     optional fused action sampling
-//   mlp_backward.inc  PPO loss gradient + dX chain of a tile, and the ONE-launch forward+backward
+//                     optional fused action sampling; written once over ArithF32 / ArithB3 (there too)
+//   mlp_backward.inc  PPO loss gradient + dX chain of a tile (once, over the same two), and the ONE-launch forward+backward
 //                     kernel whose backward workgroups wait on per-tile flags of the forward ones
 //   mlp_grad_w.inc    dW = dZ^T A over row slabs (one partial per workgroup) + fixed-order reduction
 //   mlp_fused_step.inc  ONE persistent launch per minibatch: forward, loss, dX chain and dW of every tile in the workgroup
@@ -52,8 +52,8 @@ namespace {
 // 32-env shape.  The actions go through HBM rows the workgroup itself just wrote (it waits for its
 // stores and re-reads them: same CU, and nothing has read those lines since the kernel began).
 // Bit for bit what mlp_forward_sample followed by fly_step leave.
-constexpr int RS_LDS_FLOATS = FWD_LDS_FLOATS > ENVS_PER_BLOCK * FLY_NUM_OBS ? FWD_LDS_FLOATS : ENVS_PER_BLOCK * FLY_NUM_OBS;
-constexpr int RS_B3_LDS_FLOATS = FWD_B3_LDS_FLOATS > ENVS_PER_BLOCK * FLY_NUM_OBS ? FWD_B3_LDS_FLOATS : ENVS_PER_BLOCK * FLY_NUM_OBS;
+template <class Arith>       // the policy's arena, or the env step's observation block where that is larger
+constexpr int RS_LDS_FLOATS = Arith::FWD_FLOATS > ENVS_PER_BLOCK * FLY_NUM_OBS ? Arith::FWD_FLOATS : ENVS_PER_BLOCK * FLY_NUM_OBS;
 static_assert(ENVS_PER_BLOCK == BM && BLOCK == THREADS, "one forward tile = one env block");
 constexpr int NORM_LDS_FLOATS = OBS_NORM_TABLE + 1;     // the NORM instantiations' copy of the normalisation table (obs_norm.h)
 static_assert(MLP_IN == OBS_NORM_COLS && OBS_NORM_TABLE <= THREADS, "one table entry per thread");
@@ -68,7 +68,8 @@ __global__ __launch_bounds__(THREADS, B3 ? 1 : 2) void rollout_step_kernel(
     float var_decay, float var_min, float* __restrict__ act, float* __restrict__ logp, float* __restrict__ v_out,
     const int* __restrict__ var_base)
 {
-    constexpr int ARENA = B3 ? RS_B3_LDS_FLOATS : RS_LDS_FLOATS;
+    typedef ArithOf<B3> Arith;
+    constexpr int ARENA = RS_LDS_FLOATS<Arith>;
     __shared__ __attribute__((aligned(16))) float lds[ARENA + (NORM ? NORM_LDS_FLOATS : 0)];
     float* const norm_tab = NORM ? lds + ARENA : nullptr;
     if (NORM) obs_norm_load(norm_tab, c);
@@ -77,14 +78,8 @@ __global__ __launch_bounds__(THREADS, B3 ? 1 : 2) void rollout_step_kernel(
     FlyRegs st;
     fly_load<PH_ALL, DR>(st, c, b, blockIdx.x);             // the env state's HBM round trip hides under the forward
     if (NORM) __syncthreads();                              // publishes the table
-    if (B3)
-        forward_body_b3<false, false, NORM>(lds, blockIdx.x, 1L << 40, P, static_cast<const u16*>(PF), x, n, nullptr, v_out, nullptr,
-                                            nullptr, nullptr, nullptr, eps, var, act, logp, nullptr, var_steps, var_decay, var_min,
-                                            nullptr, nullptr, false, norm_tab);
-    else
-        forward_body<false, false, NORM>(lds, blockIdx.x, 1L << 40, P, static_cast<const float*>(PF), x, n, nullptr, v_out, nullptr,
-                                         nullptr, nullptr, nullptr, eps, var, act, logp, nullptr, var_steps, var_decay, var_min,
-                                         norm_tab);
+    forward_body<Arith, false, false, NORM>(lds, blockIdx.x, 1L << 40, P, PF, x, n, nullptr, v_out, nullptr, nullptr, nullptr, nullptr, eps,
+                                            var, act, logp, nullptr, var_steps, var_decay, var_min, norm_tab);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_s_waitcnt(0);          // this thread's action stores are acknowledged by L2
     __syncthreads();
@@ -130,7 +125,8 @@ __global__ __launch_bounds__(THREADS, WPS) void rollout_all_kernel(
     float* __restrict__ reward_all, int T, const int* __restrict__ rows_applied, int64_t* __restrict__ reset_rows,
     int64_t* __restrict__ progress_rows, float* __restrict__ poses)
 {
-    constexpr int ARENA = B3 ? RS_B3_LDS_FLOATS : RS_LDS_FLOATS;
+    typedef ArithOf<B3> Arith;
+    constexpr int ARENA = RS_LDS_FLOATS<Arith>;
     __shared__ __attribute__((aligned(16))) float lds[ARENA + 32 + BM * MLP_NACT + (NORM ? NORM_LDS_FLOATS : 0)];
     float* const norm_tab = NORM ? lds + ARENA + 32 + BM * MLP_NACT : nullptr;
     if (NORM) obs_norm_load(norm_tab, c);                        // published by the barrier below
@@ -157,15 +153,10 @@ __global__ __launch_bounds__(THREADS, WPS) void rollout_all_kernel(
         b.reward = reward_all + (long)t * n;
         if (reset_rows) { b.reset = reset_rows + (long)t * n; b.progress = progress_rows + (long)t * n; }   // fly.py:175-177, per step
         const bool in_lds = B3 && whole;
-        if (B3)
-            forward_body_b3<false, false, NORM>(lds, blockIdx.x, 1L << 40, P, static_cast<const u16*>(PF), x, n, nullptr,
-                                                v_ring + (long)t * n, nullptr, nullptr, nullptr, nullptr, eps_all + (long)t * n * MLP_NACT,
-                                                varcur, act, logp_all + (long)t * n, nullptr, 0, var_decay, var_min,
-                                                in_lds && t > 0 ? lds : nullptr, in_lds ? acts : nullptr, t > 0, norm_tab);
-        else
-            forward_body<false, false, NORM>(lds, blockIdx.x, 1L << 40, P, static_cast<const float*>(PF), x, n, nullptr,
-                                             v_ring + (long)t * n, nullptr, nullptr, nullptr, nullptr, eps_all + (long)t * n * MLP_NACT,
-                                             varcur, act, logp_all + (long)t * n, nullptr, 0, var_decay, var_min, norm_tab);
+        forward_body<Arith, false, false, NORM>(lds, blockIdx.x, 1L << 40, P, PF, x, n, nullptr, v_ring + (long)t * n, nullptr, nullptr,
+                                                nullptr, nullptr, eps_all + (long)t * n * MLP_NACT, varcur, act, logp_all + (long)t * n,
+                                                nullptr, 0, var_decay, var_min, norm_tab, in_lds && t > 0 ? lds : nullptr,
+                                                in_lds ? acts : nullptr, B3 && t > 0);
         if (!in_lds) {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             __builtin_amdgcn_s_waitcnt(0);      // this thread's action stores are acknowledged by L2
