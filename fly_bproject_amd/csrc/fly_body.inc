@@ -48,6 +48,115 @@ struct Root {
     float px, py, pz, qx, qy, qz, qw, vx, vy, vz, wx, wy, wz;
 };
 
+// What the step reads from FlyConfig, in the three groups the body uses them in: this lane's joint rows and the step's switches
+// (top of the step), the integrator's constants with what it derives from them (FlyDyn), and the task's scalars (reset, observation
+// and reward packs).  The derived constants are formed by the expressions the body always used, so every bit is the same.
+// fly_body takes them from a provider `k` with lane() / dyn() / task(): FlyRead reads FlyConfig where the step asks, as the
+// per-launch kernels always did; FlyConsts holds all three, fetched and derived ONCE per launch by a persistent rollout kernel in
+// front of its tile loop, so that a step reads registers.  FlyConfig does not change while a launch runs (the host setters run
+// between launches), and nothing is kept across launches.
+struct FlyLane {
+    float lo[3], hi[3], pose[3];                     // this lane's leg (lanes 6, 7: leg 0)
+    int n, reset_after;
+};
+struct FlyDyn {
+    int nsub;
+    float kp, kd, effort, vmax, mass, gravity, inertia[3], mu;   // the plain values: the DR instantiations multiply them by the env's
+    float h, hh, hJinv, minv, Iinv[3], ld, ad;                   // row every step and form 1 / mass, 1 / inertia themselves
+    float vlim, wlim, cd, cv, Lf, Lt, al0, be0;
+    float att[3], azim, sg, ab[3];                   // this lane's leg attachment and abdomen point (lanes 5..7: point 0)
+    float kc_leg, kc_abd;                            // kc on the lanes that own a point of the pass, 0 elsewhere
+};
+struct FlyTask {
+    int reward_mode, max_episode_length;
+    float dt, target[3], start_height, dof_vel_scale, up_weight, heading_weight;
+    float actions_cost_scale, energy_cost_scale, joints_at_limit_cost_scale, death_cost, termination_height, termination_height_up;
+};
+
+// PIN: hold the uniform fp32 constants in vector registers.  The persistent kernels sit at the scalar-register limit, where the
+// compiler would fetch a uniform value again at every use (a scalar load and a wait that stalls the SIMD's only wave); they have
+// vector registers to spare.  The empty asm emits nothing: it only makes the value one the compiler keeps per lane.
+template <bool PIN>
+__device__ __forceinline__ float fly_pin(float x)
+{
+    if constexpr (PIN) asm("" : "+v"(x));
+    return x;
+}
+
+// leg / abd: the leg and the abdomen point this lane owns (0 on the lanes that own none: is_leg / is_abd)
+__device__ __forceinline__ void fly_lane(FlyLane& k, const FlyConfig* c, const int leg)
+{
+    const int j0 = 3 * leg;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { k.lo[i] = c->dof_lo[j0 + i]; k.hi[i] = c->dof_hi[j0 + i]; k.pose[i] = c->dof_pose[j0 + i]; }
+    k.n = c->num_envs; k.reset_after = c->reset_after_sim;
+}
+
+template <bool PIN = false>
+__device__ __forceinline__ FlyDyn fly_dyn(const FlyConfig* c, const int leg, const int abd, const bool is_leg, const bool is_abd)
+{
+    FlyDyn k;
+    auto f = [](float x) { return fly_pin<PIN>(x); };
+    k.nsub = c->substeps;
+    const float h = c->dt / (float)k.nsub, Jinv = 1.0f / c->joint_inertia;
+    k.h = f(h); k.hh = f(0.5f * h); k.hJinv = f(h * Jinv);
+    k.kp = f(c->kp); k.kd = f(c->kd); k.effort = f(c->effort); k.vmax = f(c->vmax); k.mass = f(c->mass); k.gravity = f(c->gravity);
+    k.minv = f(1.0f / c->mass);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { k.inertia[i] = f(c->inertia[i]); k.Iinv[i] = f(1.0f / c->inertia[i]); }
+    k.vlim = f(c->max_lin_vel); k.wlim = f(c->max_ang_vel);
+    const float kc = c->kc;
+    k.cd = f(c->cdamp); k.mu = f(c->mu); k.cv = f(c->cvisc);
+    k.Lf = f(c->femur_len); k.Lt = f(c->tibia_len);
+    k.ld = f(1.0f - h * c->lin_damp); k.ad = f(1.0f - h * c->ang_damp);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { k.att[i] = c->leg_attach[leg][i]; k.ab[i] = c->abdomen_pts[abd][i]; }
+    k.azim = c->leg_azimuth[leg]; k.sg = c->leg_sigma[leg];
+    k.al0 = f(c->alpha0); k.be0 = f(c->beta0);
+    k.kc_leg = is_leg ? kc : 0.0f; k.kc_abd = is_abd ? kc : 0.0f;
+    return k;
+}
+
+template <bool PIN = false>
+__device__ __forceinline__ FlyTask fly_task(const FlyConfig* c)
+{
+    FlyTask k;
+    auto f = [](float x) { return fly_pin<PIN>(x); };
+    k.reward_mode = c->reward_mode; k.max_episode_length = c->max_episode_length;
+    k.dt = f(c->dt); k.start_height = f(c->start_height);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) k.target[i] = f(c->target[i]);
+    k.dof_vel_scale = f(c->dof_vel_scale); k.up_weight = f(c->up_weight); k.heading_weight = f(c->heading_weight);
+    k.actions_cost_scale = f(c->actions_cost_scale); k.energy_cost_scale = f(c->energy_cost_scale);
+    k.joints_at_limit_cost_scale = f(c->joints_at_limit_cost_scale); k.death_cost = f(c->death_cost);
+    k.termination_height = f(c->termination_height); k.termination_height_up = f(c->termination_height_up);
+    return k;
+}
+
+struct FlyRead {
+    const FlyConfig* c;
+    __device__ __forceinline__ void lane(FlyLane& k, int leg) const { fly_lane(k, c, leg); }
+    __device__ __forceinline__ FlyDyn dyn(int leg, int abd, bool is_leg, bool is_abd) const { return fly_dyn(c, leg, abd, is_leg, is_abd); }
+    __device__ __forceinline__ FlyTask task() const { return fly_task(c); }
+};
+struct FlyConsts {
+    FlyLane l;
+    FlyDyn d;
+    FlyTask t;
+    // this thread's: a lane's role (and so its rows of the tables) is the same in every tile and step
+    __device__ __forceinline__ explicit FlyConsts(const FlyConfig* c)
+    {
+        const int sub = threadIdx.x & (LANES_PER_ENV - 1);
+        const bool is_leg = sub < FLY_NUM_LEGS, is_abd = sub < FLY_NUM_ABDOMEN;
+        fly_lane(l, c, is_leg ? sub : 0);
+        d = fly_dyn<true>(c, is_leg ? sub : 0, is_abd ? sub : 0, is_leg, is_abd);
+        t = fly_task<true>(c);
+    }
+    __device__ __forceinline__ void lane(FlyLane& k, int) const { k = l; }
+    __device__ __forceinline__ const FlyDyn& dyn(int, int, bool, bool) const { return d; }
+    __device__ __forceinline__ const FlyTask& task() const { return t; }
+};
+
 // ---- K4 helpers: separately rounded fp32 (the file is built with -ffp-contract=off; every fused
 // multiply-add in the physics is an explicit fmaf, so all template instances round identically) --
 __device__ __forceinline__ void quat_rot(const float q[4], float v0, float v1, float v2, float sign, float o[3])
@@ -75,13 +184,13 @@ struct RootObs {
 };
 
 // fly.py:771-805 root-derived part (compute_heading_and_up, compute_rot, get_euler_xyz)
-__device__ __forceinline__ RootObs root_obs(const FlyConfig* __restrict__ c, const Root& r)
+__device__ __forceinline__ RootObs root_obs(const FlyTask& c, const Root& r)
 {
     RootObs o;
     const float two_pi = 6.28318530717958647692f;
-    float t0 = c->target[0] - r.px, t1 = c->target[1] - r.py, t2 = 0.0f;
+    float t0 = c.target[0] - r.px, t1 = c.target[1] - r.py, t2 = 0.0f;
     float nrm = sqrtf(t0 * t0 + t1 * t1 + t2 * t2);
-    o.pot = -nrm / c->dt;
+    o.pot = -nrm / c.dt;
     float dn = nrm < 1e-9f ? 1e-9f : nrm;
     float d0 = t0 / dn, d1 = t1 / dn, d2 = t2 / dn;
     // quat_mul(torso_rotation, inv_start_rot), inv_start_rot = conj(0,0,0,1)
@@ -122,7 +231,7 @@ __device__ __forceinline__ RootObs root_obs(const FlyConfig* __restrict__ c, con
     o.roll = py_mod(roll, two_pi);
     o.pitch = py_mod(pitch, two_pi);
     o.yaw = py_mod(yaw, two_pi);
-    float walk = atan2f(c->target[2] - r.pz, c->target[0] - r.px);
+    float walk = atan2f(c.target[2] - r.pz, c.target[0] - r.px);
     o.ang = walk - o.yaw;
     return o;
 }
@@ -149,6 +258,73 @@ struct FlyRegs {
     float dm[FLY_DR_PARAMS];
     uint32_t dk;
 };
+
+// What a step otherwise stores and never reads back: the env's episode accumulators (zeros when off), this lane's targets and its two
+// contact forces.  The persistent rollout kernels carry them beside FlyRegs (fly_load_carry, fly_body's `cy`, fly_store_carried).
+struct FlyCarry {
+    float ep_return, ep_length, done_return, done_length, done_count;
+    float jt0, jt1, jt2, cf0, cf1, cf2, cfa0, cfa1, cfa2;
+};
+struct FlyNoCarry {};      // the per-launch kernels: every step stores its state and updates the accumulators in memory
+
+// The state tensors a step leaves: targets, dof_state, root, contact of env `e`, each value from the lane that owns it (pot and
+// prev_pot go with the caller's flag lane).  fly_body stores them at every step; a persistent rollout kernel once per tile, behind
+// the tile's last step (fly_store_carried).
+template <int PH>
+__device__ __forceinline__ void fly_store_state(const FlyBuffers& b, const long e, const int sub, const float (&jt)[3], const float (&jq)[3],
+                                                const float (&jqd)[3], const Root& r, const float (&cf)[3], const float (&cfa)[3])
+{
+    const bool is_leg = sub < FLY_NUM_LEGS, is_abd = sub < FLY_NUM_ABDOMEN;
+    const int leg = is_leg ? sub : 0, abd = is_abd ? sub : 0, j0 = 3 * leg;
+    if (PH & (PH_SCALE)) {
+        if (is_leg) {
+            float* tp = b.targets + e * FLY_NUM_DOF + j0;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) tp[i] = jt[i];
+        }
+    }
+    if (PH & (PH_RESET | PH_INTEGRATE)) {
+        if (is_leg) {
+            float* dp = b.dof_state + e * (FLY_NUM_DOF * 2) + 2 * j0;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) { dp[2 * i] = jq[i]; dp[2 * i + 1] = jqd[i]; }
+        }
+        if (sub == LANES_PER_ENV - 1) {
+            float* rp = b.root + e * FLY_ROOT_DIM;
+            rp[0] = r.px; rp[1] = r.py; rp[2] = r.pz; rp[3] = r.qx; rp[4] = r.qy; rp[5] = r.qz; rp[6] = r.qw;
+            rp[7] = r.vx; rp[8] = r.vy; rp[9] = r.vz; rp[10] = r.wx; rp[11] = r.wy; rp[12] = r.wz;
+        }
+    }
+    if (PH & PH_INTEGRATE) {
+        if (is_leg) {
+            float* fp = b.contact + (e * FLY_NUM_CONTACT + FLY_NUM_ABDOMEN + leg) * 3;
+            fp[0] = cf[0]; fp[1] = cf[1]; fp[2] = cf[2];
+        }
+        if (is_abd) {
+            float* fp = b.contact + (e * FLY_NUM_CONTACT + abd) * 3;
+            fp[0] = cfa[0]; fp[1] = cfa[1]; fp[2] = cfa[2];
+        }
+    }
+}
+
+// What a persistent rollout kernel carried through a tile's T steps (FlyRegs, and the FlyCarry fly_body updated), stored behind the last of them:
+// the state tensors and, when they are on, the episode accumulators.  Bit for bit what the last step's own stores would leave.
+template <int PH>
+__device__ __forceinline__ void fly_store_carried(const FlyBuffers& b, const int block, const int n, const FlyRegs& st, const FlyCarry& cy)
+{
+    const int sub = threadIdx.x & (LANES_PER_ENV - 1);
+    const long e = (long)block * ENVS_PER_BLOCK + threadIdx.x / LANES_PER_ENV;
+    if (e >= n) return;                          // tail lanes shadow env n - 1 and store nothing
+    const float jt[3] = {cy.jt0, cy.jt1, cy.jt2}, jq[3] = {st.jq[0], st.jq[1], st.jq[2]}, jqd[3] = {st.jqd[0], st.jqd[1], st.jqd[2]};
+    const float cf[3] = {cy.cf0, cy.cf1, cy.cf2}, cfa[3] = {cy.cfa0, cy.cfa1, cy.cfa2};
+    fly_store_state<PH>(b, e, sub, jt, jq, jqd, st.r, cf, cfa);
+    if (sub != LANES_PER_ENV - 2) return;
+    b.pot[e] = st.pot; b.prev_pot[e] = st.prev_pot;
+    if (b.ep_return) {
+        b.ep_return[e] = cy.ep_return; b.ep_length[e] = cy.ep_length;
+        b.done_return[e] = cy.done_return; b.done_length[e] = cy.done_length; b.done_count[e] = cy.done_count;
+    }
+}
 
 // DR: per-env physics domain randomisation (fly_set_randomization): the phases that reset or integrate read the env's row
 template <int PH, bool DR = false>
@@ -189,35 +365,53 @@ __device__ __forceinline__ void fly_load(FlyRegs& st, const FlyConfig* __restric
     if constexpr (DR && (PH & (PH_RESET | PH_INTEGRATE)) != 0) dr_load_row(c, e, st.dm, st.dk);
 }
 
+// the episode accumulators of this lane's env, read once per tile; a null ep_return keeps meaning "off" (zeros, never stored)
+__device__ __forceinline__ void fly_load_carry(FlyCarry& cy, const FlyConfig* __restrict__ c, const FlyBuffers& b, const int block)
+{
+    const int n = c->num_envs;
+    const long e_raw = (long)block * ENVS_PER_BLOCK + threadIdx.x / LANES_PER_ENV;
+    const long e = e_raw < n ? e_raw : (long)(n - 1);
+    cy = FlyCarry{};
+    if (b.ep_return) {
+        cy.ep_return = b.ep_return[e]; cy.ep_length = b.ep_length[e];
+        cy.done_return = b.done_return[e]; cy.done_length = b.done_length[e]; cy.done_count = b.done_count[e];
+    }
+}
+
 // `st_out` (optional): the state the step leaves, back in registers -- the one-launch-per-ROLLOUT kernel carries it
 // from step to step instead of re-reading what it has just stored.
 // DR: FlyDyn runs on the env's multiplied constants (st.dm), and every reset draws the env's next row, which one lane stores
 // (tail lanes that shadow env n - 1 do not): before the physics when resets come first, so that the new draw drives this
 // step; after it with reset_after_sim, so that it applies from the next step.
-template <int PH, bool DR = false>
-__device__ __forceinline__ void fly_body(const FlyConfig* __restrict__ c, const float* __restrict__ actions, const FlyBuffers& b,
-                                         float* obs_tile, const int block, const FlyRegs& st, FlyRegs* st_out = nullptr,
-                                         const float* actions_tile = nullptr)
+// K: FlyRead{c} (the per-launch kernels) or the caller's FlyConsts; `c` itself is read by the DR draws only.
+// cy (a FlyCarry: the persistent rollout kernels, with st_out): the step stores its rows (obs, reward, reset, progress: the update
+// reads them) but neither the state tensors nor the episode accumulators: those leave in st_out and cy, which the step updates in
+// place, and the caller stores them once behind the tile's last step (fly_store_carried) -- nothing reads them before the launch ends.
+template <int PH, bool DR = false, class Consts, class Carry = FlyNoCarry>
+__device__ __forceinline__ void fly_body(const FlyConfig* __restrict__ c, const Consts& K, const float* __restrict__ actions,
+                                         const FlyBuffers& b, float* obs_tile, const int block, const FlyRegs& st,
+                                         FlyRegs* st_out = nullptr, const float* actions_tile = nullptr, Carry* cy = nullptr)
 {
+    constexpr bool CARRY = std::is_same<Carry, FlyCarry>::value;
     // actions_tile (one-launch rollout): this workgroup's 32 x 18 actions in LDS, left there by the policy body that ran just before
 
-    const int n = c->num_envs;
     const int tid = threadIdx.x;
     const int sub = tid & (LANES_PER_ENV - 1);
     const int env_in_blk = tid / LANES_PER_ENV;
-    const long e_raw = (long)block * ENVS_PER_BLOCK + env_in_blk;
-    const bool valid = e_raw < n;
-    const long e = valid ? e_raw : (long)(n - 1);   // tail lanes shadow the last env; stores are masked
     const bool is_leg = sub < FLY_NUM_LEGS;
     const bool is_abd = sub < FLY_NUM_ABDOMEN;             // the first five lanes also own an abdomen point
     const int leg = is_leg ? sub : 0;
     const int abd = is_abd ? sub : 0;
     const int j0 = 3 * leg;
+    FlyLane kl;
+    K.lane(kl, leg);
+    const int n = kl.n;
+    const long e_raw = (long)block * ENVS_PER_BLOCK + env_in_blk;
+    const bool valid = e_raw < n;
+    const long e = valid ? e_raw : (long)(n - 1);   // tail lanes shadow the last env; stores are masked
 
     // per-lane tables
-    float lo[3], hi[3], pose[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { lo[i] = c->dof_lo[j0 + i]; hi[i] = c->dof_hi[j0 + i]; pose[i] = c->dof_pose[j0 + i]; }
+    const float (&lo)[3] = kl.lo, (&hi)[3] = kl.hi, (&pose)[3] = kl.pose;
 
     // ---- state: requested by fly_load ----------------------------------------------------------
     Root r = st.r;
@@ -260,18 +454,19 @@ __device__ __forceinline__ void fly_body(const FlyConfig* __restrict__ c, const 
         }
     }
 
-    const bool reset_after = c->reset_after_sim != 0;
+    const bool reset_after = kl.reset_after != 0;
 
     auto do_reset = [&]() {
         // fly.py:446-480: flagged envs go back to the reset pose; potentials recomputed; flags cleared
         if (rs) {
-            r.px = 0.0f; r.py = 0.0f; r.pz = c->start_height; r.qx = 0.0f; r.qy = 0.0f; r.qz = 0.0f; r.qw = 1.0f;
+            const FlyTask& k = K.task();
+            r.px = 0.0f; r.py = 0.0f; r.pz = k.start_height; r.qx = 0.0f; r.qy = 0.0f; r.qz = 0.0f; r.qw = 1.0f;
             r.vx = r.vy = r.vz = r.wx = r.wy = r.wz = 0.0f;
 #pragma unroll
             for (int i = 0; i < 3; ++i) { jq[i] = is_leg ? pose[i] : 0.0f; jqd[i] = 0.0f; }
-            float tx = c->target[0] - 0.0f, ty = c->target[1] - 0.0f;
+            float tx = k.target[0] - 0.0f, ty = k.target[1] - 0.0f;
             float nrm = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(tx, tx), __fmul_rn(ty, ty)), 0.0f));
-            float p = -nrm / c->dt;
+            float p = -nrm / k.dt;
             prev_pot = p; pot = p;
             rs = 0; progress = 0;
             if constexpr (DR) {
@@ -286,25 +481,26 @@ __device__ __forceinline__ void fly_body(const FlyConfig* __restrict__ c, const 
 
     // ---- K3: FlyDyn substeps in registers ----------------------------------------------------
     if (PH & PH_INTEGRATE) {
-        const int nsub = c->substeps;
-        const float h = c->dt / (float)nsub;
+        const FlyDyn& k = K.dyn(leg, abd, is_leg, is_abd);
+        const int nsub = k.nsub;
+        const float h = k.h, hJinv = k.hJinv, hh = k.hh;
         // DR: the env's constants, one fp32 product each, formed once per env step (the substep loop is the plain one)
-        const float kp = DR ? __fmul_rn(c->kp, dm[0]) : c->kp, kd = DR ? __fmul_rn(c->kd, dm[1]) : c->kd;
-        const float eff = DR ? __fmul_rn(c->effort, dm[2]) : c->effort, vmax = c->vmax, Jinv = 1.0f / c->joint_inertia;
-        const float minv = 1.0f / (DR ? __fmul_rn(c->mass, dm[3]) : c->mass), g = DR ? __fmul_rn(c->gravity, dm[5]) : c->gravity;
-        const float I0 = DR ? __fmul_rn(c->inertia[0], dm[3]) : c->inertia[0];
-        const float I1 = DR ? __fmul_rn(c->inertia[1], dm[3]) : c->inertia[1];
-        const float I2 = DR ? __fmul_rn(c->inertia[2], dm[3]) : c->inertia[2];
-        const float I0inv = 1.0f / I0, I1inv = 1.0f / I1, I2inv = 1.0f / I2;
-        const float vlim = c->max_lin_vel, wlim = c->max_ang_vel;
-        const float kc = c->kc, cd = c->cdamp, mu = DR ? __fmul_rn(c->mu, dm[4]) : c->mu, cv = c->cvisc;
-        const float Lf = c->femur_len, Lt = c->tibia_len;
-        const float ld = 1.0f - h * c->lin_damp, ad = 1.0f - h * c->ang_damp;
-        const float att0 = c->leg_attach[leg][0], att1 = c->leg_attach[leg][1], att2 = c->leg_attach[leg][2];
-        const float azim = c->leg_azimuth[leg], sg = c->leg_sigma[leg];
-        const float ab0 = c->abdomen_pts[abd][0], ab1 = c->abdomen_pts[abd][1], ab2 = c->abdomen_pts[abd][2];
-        const float al0 = c->alpha0, be0 = c->beta0;
-        const float kc_leg = is_leg ? kc : 0.0f, kc_abd = is_abd ? kc : 0.0f;
+        const float kp = DR ? __fmul_rn(k.kp, dm[0]) : k.kp, kd = DR ? __fmul_rn(k.kd, dm[1]) : k.kd;
+        const float eff = DR ? __fmul_rn(k.effort, dm[2]) : k.effort, vmax = k.vmax;
+        const float minv = DR ? 1.0f / __fmul_rn(k.mass, dm[3]) : k.minv, g = DR ? __fmul_rn(k.gravity, dm[5]) : k.gravity;
+        const float I0 = DR ? __fmul_rn(k.inertia[0], dm[3]) : k.inertia[0];
+        const float I1 = DR ? __fmul_rn(k.inertia[1], dm[3]) : k.inertia[1];
+        const float I2 = DR ? __fmul_rn(k.inertia[2], dm[3]) : k.inertia[2];
+        const float I0inv = DR ? 1.0f / I0 : k.Iinv[0], I1inv = DR ? 1.0f / I1 : k.Iinv[1], I2inv = DR ? 1.0f / I2 : k.Iinv[2];
+        const float vlim = k.vlim, wlim = k.wlim;
+        const float cd = k.cd, mu = DR ? __fmul_rn(k.mu, dm[4]) : k.mu, cv = k.cv;
+        const float Lf = k.Lf, Lt = k.Lt;
+        const float ld = k.ld, ad = k.ad;
+        const float att0 = k.att[0], att1 = k.att[1], att2 = k.att[2];
+        const float azim = k.azim, sg = k.sg;
+        const float ab0 = k.ab[0], ab1 = k.ab[1], ab2 = k.ab[2];
+        const float al0 = k.al0, be0 = k.be0;
+        const float kc_leg = k.kc_leg, kc_abd = k.kc_abd;
 
         for (int s = 0; s < nsub; ++s) {
             // 1. joints (leg lanes; the others integrate zeros)
@@ -312,7 +508,7 @@ __device__ __forceinline__ void fly_body(const FlyConfig* __restrict__ c, const 
             for (int i = 0; i < 3; ++i) {
                 float tau = fmaf(kp, jt[i] - jq[i], -(kd * jqd[i]));
                 tau = fminf(fmaxf(tau, -eff), eff);
-                float v = fmaf(h * Jinv, tau, jqd[i]);
+                float v = fmaf(hJinv, tau, jqd[i]);
                 v = fminf(fmaxf(v, -vmax), vmax);
                 float x = fmaf(h, v, jq[i]);
                 if (x < lo[i]) { x = lo[i]; v = fmaxf(v, 0.0f); }
@@ -395,7 +591,6 @@ __device__ __forceinline__ void fly_body(const FlyConfig* __restrict__ c, const 
             r.wy = dot3(R10, R11, R12, wbx, wby, wbz);
             r.wz = dot3(R20, R21, R22, wbx, wby, wbz);
             r.px = fmaf(h, r.vx, r.px); r.py = fmaf(h, r.vy, r.py); r.pz = fmaf(h, r.vz, r.pz);
-            const float hh = 0.5f * h;
             float nqx = fmaf(hh, fmaf(r.wx, qw, fmaf(r.wy, qz, -(r.wz * qy))), qx);
             float nqy = fmaf(hh, fmaf(-r.wx, qz, fmaf(r.wy, qw, r.wz * qx)), qy);
             float nqz = fmaf(hh, fmaf(r.wx, qy, fmaf(-r.wy, qx, r.wz * qw)), qz);
@@ -413,7 +608,8 @@ __device__ __forceinline__ void fly_body(const FlyConfig* __restrict__ c, const 
     float z_obs = 0.0f, heading_proj = 0.0f;
     if (PH & PH_OBS) {
         prev_pot = pot;                                   // fly.py:786
-        RootObs ro = root_obs(c, r);
+        const FlyTask& k = K.task();
+        RootObs ro = root_obs(k, r);
         pot = ro.pot;                                     // fly.py:787
         float* row = obs_tile + env_in_blk * FLY_NUM_OBS;
         if (sub == LANES_PER_ENV - 1) {
@@ -424,7 +620,7 @@ __device__ __forceinline__ void fly_body(const FlyConfig* __restrict__ c, const 
         }
         z_obs = r.pz; heading_proj = ro.heading_proj;
         if (is_leg) {
-            const float vs = c->dof_vel_scale;
+            const float vs = k.dof_vel_scale;
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
                 // unscale(): (2x - hi - lo)/(hi - lo), separately rounded
@@ -469,7 +665,8 @@ __device__ __forceinline__ void fly_body(const FlyConfig* __restrict__ c, const 
     float reward = 0.0f;
     if (PH & PH_REWARD) {
         if (progress == 0) progress = 1;                   // fly.py:415-416
-        const float uw = c->up_weight, hw = c->heading_weight;
+        const FlyTask& k = K.task();
+        const float uw = k.up_weight, hw = k.heading_weight;
         float elec = 0.0f, acost = 0.0f;
         int lim = 0, touching = 0;
         if (is_leg) {
@@ -499,23 +696,40 @@ __device__ __forceinline__ void fly_body(const FlyConfig* __restrict__ c, const 
         float leg_r = __fmul_rn((float)touching, 0.1f);
         float progress_r = __fsub_rn(pot, prev_pot);
         float total;
-        if (c->reward_mode == 0) {                         // fly.py:750
+        if (k.reward_mode == 0) {                         // fly.py:750
             total = __fadd_rn(0.5f, __fmul_rn(up_r, orient_r));
-            total = __fsub_rn(total, __fmul_rn(c->energy_cost_scale, elec));
-            total = __fsub_rn(total, __fmul_rn((float)lim, c->joints_at_limit_cost_scale));
+            total = __fsub_rn(total, __fmul_rn(k.energy_cost_scale, elec));
+            total = __fsub_rn(total, __fmul_rn((float)lim, k.joints_at_limit_cost_scale));
             total = __fadd_rn(total, leg_r);
         } else {                                           // fly.py:747-748
             total = __fadd_rn(__fmul_rn(progress_r, 2.0f), 0.5f);
             total = __fadd_rn(total, __fmul_rn(up_r, orient_r));
             total = __fadd_rn(total, heading_r);
-            total = __fsub_rn(total, __fmul_rn(c->actions_cost_scale, acost));
-            total = __fsub_rn(total, __fmul_rn(c->energy_cost_scale, elec));
-            total = __fsub_rn(total, __fmul_rn((float)lim, c->joints_at_limit_cost_scale));
+            total = __fsub_rn(total, __fmul_rn(k.actions_cost_scale, acost));
+            total = __fsub_rn(total, __fmul_rn(k.energy_cost_scale, elec));
+            total = __fsub_rn(total, __fmul_rn((float)lim, k.joints_at_limit_cost_scale));
         }
-        const bool dead = (z < c->termination_height) || (z > c->termination_height_up) || (ori < 0.5f) || (abd_sum > 0.0f);
-        if (dead) total = c->death_cost;                   // fly.py:753-756
-        if (dead || progress >= (long)c->max_episode_length - 1) rs = 1;   // fly.py:759-766
+        const bool dead = (z < k.termination_height) || (z > k.termination_height_up) || (ori < 0.5f) || (abd_sum > 0.0f);
+        if (dead) total = k.death_cost;                   // fly.py:753-756
+        if (dead || progress >= (long)k.max_episode_length - 1) rs = 1;   // fly.py:759-766
         reward = total;
+    }
+
+    // carried: the episode statistics (optional) on the accumulators in `cy` -- the additions of the store section below, in its
+    // order, on every lane of the env (reward and rs are the same bits on all eight) -- and what the state stores will need
+    if constexpr (CARRY) {
+        if ((PH & PH_REWARD) && b.ep_return) {
+            const float er = cy->ep_return + reward, el = cy->ep_length + 1.0f;
+            if (rs) {
+                cy->done_return += er; cy->done_length += el; cy->done_count += 1.0f;
+                cy->ep_return = 0.0f; cy->ep_length = 0.0f;
+            } else {
+                cy->ep_return = er; cy->ep_length = el;
+            }
+        }
+        cy->jt0 = jt[0]; cy->jt1 = jt[1]; cy->jt2 = jt[2];
+        cy->cf0 = cf[0]; cy->cf1 = cf[1]; cy->cf2 = cf[2];
+        cy->cfa0 = cfa[0]; cy->cfa1 = cfa[1]; cy->cfa2 = cfa[2];
     }
 
     if (st_out) {
@@ -534,42 +748,14 @@ __device__ __forceinline__ void fly_body(const FlyConfig* __restrict__ c, const 
     if constexpr (DR) {
         if (drew && sub == 0) dr_store_row(c, e, dm, dk);
     }
-    if (PH & (PH_SCALE)) {
-        if (is_leg) {
-            float* tp = b.targets + e * FLY_NUM_DOF + j0;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) tp[i] = jt[i];
-        }
-    }
-    if (PH & (PH_RESET | PH_INTEGRATE)) {
-        if (is_leg) {
-            float* dp = b.dof_state + e * (FLY_NUM_DOF * 2) + 2 * j0;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) { dp[2 * i] = jq[i]; dp[2 * i + 1] = jqd[i]; }
-        }
-        if (sub == LANES_PER_ENV - 1) {
-            float* rp = b.root + e * FLY_ROOT_DIM;
-            rp[0] = r.px; rp[1] = r.py; rp[2] = r.pz; rp[3] = r.qx; rp[4] = r.qy; rp[5] = r.qz; rp[6] = r.qw;
-            rp[7] = r.vx; rp[8] = r.vy; rp[9] = r.vz; rp[10] = r.wx; rp[11] = r.wy; rp[12] = r.wz;
-        }
-    }
-    if (PH & PH_INTEGRATE) {
-        if (is_leg) {
-            float* fp = b.contact + (e * FLY_NUM_CONTACT + FLY_NUM_ABDOMEN + leg) * 3;
-            fp[0] = cf[0]; fp[1] = cf[1]; fp[2] = cf[2];
-        }
-        if (is_abd) {
-            float* fp = b.contact + (e * FLY_NUM_CONTACT + abd) * 3;
-            fp[0] = cfa[0]; fp[1] = cfa[1]; fp[2] = cfa[2];
-        }
-    }
+    if constexpr (!CARRY) fly_store_state<PH>(b, e, sub, jt, jq, jqd, r, cf, cfa);
     if (sub == LANES_PER_ENV - 2) {
-        if (PH & (PH_RESET | PH_OBS)) { b.pot[e] = pot; b.prev_pot[e] = prev_pot; }
+        if (!CARRY && (PH & (PH_RESET | PH_OBS))) { b.pot[e] = pot; b.prev_pot[e] = prev_pot; }
         if (PH & (PH_RESET | PH_REWARD)) b.reset[e] = (int64_t)rs;
         if (PH & (PH_RESET | PH_REWARD | PH_PROGRESS)) b.progress[e] = (int64_t)progress;
         if (PH & PH_REWARD) {
             b.reward[e] = reward;
-            if (b.ep_return) {        // episode statistics (optional)
+            if (!CARRY && b.ep_return) {        // episode statistics (optional)
                 const float er = b.ep_return[e] + reward, el = b.ep_length[e] + 1.0f;
                 if (rs) {
                     b.done_return[e] += er; b.done_length[e] += el; b.done_count[e] += 1.0f;

@@ -39,7 +39,7 @@ __global__ __launch_bounds__(BLOCK) void fly_kernel(const FlyConfig* __restrict_
     __shared__ __attribute__((aligned(16))) float obs_tile[ENVS_PER_BLOCK * FLY_NUM_OBS];
     FlyRegs st;
     fly_load<PH>(st, c, b, blockIdx.x);
-    fly_body<PH>(c, actions, b, obs_tile, blockIdx.x, st);
+    fly_body<PH>(c, FlyRead{c}, actions, b, obs_tile, blockIdx.x, st);
 }
 
 // the randomising instantiations (fly_set_randomization) of the phase sets that reset or integrate; a kernel of its own name so
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(BLOCK) void fly_dr_kernel(const FlyConfig* __restri
     __shared__ __attribute__((aligned(16))) float obs_tile[ENVS_PER_BLOCK * FLY_NUM_OBS];
     FlyRegs st;
     fly_load<PH, true>(st, c, b, blockIdx.x);
-    fly_body<PH, true>(c, actions, b, obs_tile, blockIdx.x, st);
+    fly_body<PH, true>(c, FlyRead{c}, actions, b, obs_tile, blockIdx.x, st);
 }
 
 inline int grid_for(int n) { return (n + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK; }

@@ -83,7 +83,7 @@ __global__ __launch_bounds__(THREADS, B3 ? 1 : 2) void rollout_step_kernel(
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_s_waitcnt(0);          // this thread's action stores are acknowledged by L2
     __syncthreads();
-    fly_body<PH_ALL, DR>(c, act, b, lds, blockIdx.x, st);
+    fly_body<PH_ALL, DR>(c, FlyRead{c}, act, b, lds, blockIdx.x, st);
 }
 
 // Pose record (fly_set_pose_record): env 0's pose after step t -- root position, quaternion xyzw, the 18 joint angles in DoF
@@ -144,6 +144,8 @@ __global__ __launch_bounds__(THREADS, WPS) void rollout_all_kernel(
     if (threadIdx.x < MLP_NACT) varcur[threadIdx.x] = var[threadIdx.x];
     FlyRegs st;
     fly_load<PH_ALL, DR>(st, c, b, blockIdx.x);
+    FlyCarry cy;                                                 // the episode accumulators and what the state stores need: stored after step T - 1
+    fly_load_carry(cy, c, b, blockIdx.x);
     __syncthreads();
     const bool whole = (long)(blockIdx.x + 1) * BM <= n;         // a ragged last tile keeps the HBM hand-offs (its LDS rows are partly stale)
     for (int t = 0; t < T; ++t) {
@@ -162,14 +164,17 @@ __global__ __launch_bounds__(THREADS, WPS) void rollout_all_kernel(
             __builtin_amdgcn_s_waitcnt(0);      // this thread's action stores are acknowledged by L2
         }
         __syncthreads();
+        // FlyConfig is still read step by step here: this kernel's registers are full (fetching it once spills)
         FlyRegs nx;
-        fly_body<PH_ALL, DR>(c, act, b, lds, blockIdx.x, st, &nx, in_lds ? acts : nullptr);
+        fly_body<PH_ALL, DR>(c, FlyRead{c}, act, b, lds, blockIdx.x, st, &nx, in_lds ? acts : nullptr, &cy);
         if (REC && blockIdx.x == 0) store_pose(poses, t, nx);
         st = nx;
         if (threadIdx.x < MLP_NACT && var_decay > 0.0f) varcur[threadIdx.x] = fmaxf(var_min, varcur[threadIdx.x] - var_decay);
         if (!in_lds) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // observation row t + 1 is in L2 before any wave of this workgroup reads it
         __syncthreads();
     }
+    // the env's state tensors and episode accumulators: nothing reads them before the launch ends, so they are stored once, here
+    if (T > 0) fly_store_carried<PH_ALL>(b, blockIdx.x, (int)n, st, cy);
 }
 
 // The same loop with the policy in the fused step's style (policy_tile_fs, mlp_fused_step.inc): swizzled plane images, the chain
@@ -206,6 +211,7 @@ __global__ __launch_bounds__(THREADS, 1) void rollout_all_fs_kernel(
     int64_t* const reset0 = b.reset;                          // the CURRENT flags: read once per tile, before the tile's step 0
     int64_t* const progress0 = b.progress;
     const long ntiles = n / BM;                               // whole tiles only (the launcher checks)
+    const FlyConsts k(c);                                   // once per launch, in front of the tile loop: no step reads FlyConfig
     // persistent over tiles: workgroup g runs the T steps of tiles g, g + grid, ... one after the other (one tile per workgroup at
     // <= 8192 envs on 256 CUs; two at 16384).  Tiles are independent, so the order is free and every row equals the per-step launches'.
     long tile = blockIdx.x;
@@ -215,6 +221,8 @@ __global__ __launch_bounds__(THREADS, 1) void rollout_all_fs_kernel(
         b.reset = reset0; b.progress = progress0;
         FlyRegs st;
         fly_load<PH_ALL, DR>(st, c, b, (int)tile);
+        FlyCarry cy;                                          // the episode accumulators and what the state stores need: stored after step T - 1
+        fly_load_carry(cy, c, b, (int)tile);
         WeightHeadT<2> w1;
         policy_tile_fs_head(w1, PB);
         __syncthreads();
@@ -231,12 +239,14 @@ __global__ __launch_bounds__(THREADS, 1) void rollout_all_fs_kernel(
             policy_tile_fs_head(w1, PB);     // the NEXT step's first weights: their round trip hides under the physics (A/B: requested
                                              // after the env step; not kept)
             FlyRegs nx;
-            fly_body<PH_ALL, DR>(c, act, b, L.obs, (int)tile, st, &nx, L.acts);
+            fly_body<PH_ALL, DR>(c, k, act, b, L.obs, (int)tile, st, &nx, L.acts, &cy);
             if (REC && tile == 0) store_pose(poses, t, nx);
             st = nx;
             if (threadIdx.x < MLP_NACT && var_decay > 0.0f) L.varcur[threadIdx.x] = fmaxf(var_min, L.varcur[threadIdx.x] - var_decay);
             __syncthreads();
         }
+        // the tile's state tensors and episode accumulators: nothing reads them before the launch ends, so they are stored once, here
+        if (T > 0) fly_store_carried<PH_ALL>(b, (int)tile, (int)n, st, cy);
         stamp<STAMP>(st_tile, 8 * T);
         if (STAMP && threadIdx.x == 0) st_tile[8 * T + 1] = realtime_cu();
         tile += gridDim.x;
